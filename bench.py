@@ -1,6 +1,11 @@
 """Flagship training benchmark (driver contract).
 
   python bench.py --gpus N --steps K --warmup W [--model llama3-8b]
+                  [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps, writes the last step's
+outputs if --dump-outputs is given and prints one JSON result line; anything
+measured beyond that headline figure belongs behind --full.
 
 Measures the BASELINE.json metric: whole-node tokens/s (+ MFU) for
 Llama-3-8B / 70B on synthetic data of the benchmark shape with random-init
@@ -82,7 +87,57 @@ def parse_args():
                    help="run hipBLASLt TunableOp algo search and save profiles/tunableop_gfx950.csv")
     p.add_argument("--no-tunableop", action="store_true",
                    help="skip loading the committed TunableOp GEMM selections")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps, write what the last timed step computed "
+                        "(loss, grad norm, seeded samples of the gradients and of the "
+                        "updated parameters) as DIR/<name>.npy")
+    p.add_argument("--full", action="store_true",
+                   help="also run the measurements beyond the headline figure; there are "
+                        "none yet (a plain run is set-up, warm-up, the timed steps and the "
+                        "result line), so this is where further ones belong")
     return p.parse_args()
+
+
+# elements sampled per parameter tensor by --dump-outputs: ~300 tensors in the
+# 8B model -> a few MB per array, far under the 64 MB a dump may take
+DUMP_SAMPLE_PER_TENSOR = 4096
+DUMP_SAMPLE_SEED = 20240229
+
+
+def dump_outputs(out_dir, chunks, last):
+    """Write the last timed step's results as float32/float64 .npy arrays.
+
+    A caller of train_step receives the loss and the grad norm and finds the
+    gradients (main_grad) and the updated parameters in the model; the latter
+    two are too large to store whole, so a fixed seeded sample of each tensor
+    is kept, concatenated in named_parameters() order.  The indices depend
+    only on the tensor sizes, so two builds run with the same arguments are
+    compared element for element.
+    """
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "loss.npy"), np.asarray([last["lm_loss"]], dtype=np.float64))
+    if last.get("grad_norm") is not None:
+        np.save(os.path.join(out_dir, "grad_norm.npy"),
+                np.asarray([last["grad_norm"]], dtype=np.float64))
+    gen = torch.Generator(device="cpu").manual_seed(DUMP_SAMPLE_SEED)
+    params, grads = [], []
+    for ch in chunks:
+        for _, p in ch.named_parameters():
+            n = p.numel()
+            if n <= DUMP_SAMPLE_PER_TENSOR:
+                idx = torch.arange(n)
+            else:
+                idx = torch.randint(0, n, (DUMP_SAMPLE_PER_TENSOR,), generator=gen)
+            idx = idx.to(p.device)
+            params.append(p.detach().reshape(-1)[idx].float().cpu())
+            g = getattr(p, "main_grad", None)
+            if g is not None:
+                grads.append(g.detach().reshape(-1)[idx].float().cpu())
+    np.save(os.path.join(out_dir, "params_sample.npy"), torch.cat(params).numpy())
+    if grads:
+        np.save(os.path.join(out_dir, "main_grad_sample.npy"), torch.cat(grads).numpy())
 
 
 def setup_tunableop(args, rank):
@@ -259,6 +314,9 @@ def main():
 
         tunable.write_file(tune_out)
         print(f"# wrote TunableOp results to {tune_out}", flush=True)
+
+    if args.dump_outputs and rank == 0 and last is not None:
+        dump_outputs(args.dump_outputs, chunks, last)
 
     ms_per_step = elapsed / args.steps * 1000.0
     global_batch = args.micro_batch_size * args.grad_accum * dp

@@ -128,14 +128,18 @@ _rope_cache = {}
 
 
 def rope_cos_sin(freqs: torch.Tensor):
-    key = (freqs.data_ptr(), freqs.shape)
+    key = (freqs.data_ptr(), freqs.shape, freqs.stride())
     hit = _rope_cache.get(key)
     if hit is None:
-        hit = (torch.cos(freqs).contiguous(), torch.sin(freqs).contiguous())
+        # the entry keeps `freqs` alive: a table gathered per step (inference
+        # positions) is a temporary, and once freed the allocator hands its
+        # address to the next step's table of the same shape, which must not
+        # hit the previous step's cos/sin
+        hit = (torch.cos(freqs).contiguous(), torch.sin(freqs).contiguous(), freqs)
         _rope_cache[key] = hit
         if len(_rope_cache) > 8:
             _rope_cache.pop(next(iter(_rope_cache)))
-    return hit
+    return hit[:2]
 
 
 def rope_apply(x: torch.Tensor, freqs: torch.Tensor) -> torch.Tensor:

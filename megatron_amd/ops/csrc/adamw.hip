@@ -41,7 +41,7 @@ __global__ void adamw_kernel(const TensorPtrs* __restrict__ tensors,
 
 __global__ void l2norm_kernel(const float* const* __restrict__ ptrs, const long* __restrict__ lens,
                               const int2* __restrict__ chunks, int n_chunks,
-                              float* __restrict__ out_sq) {
+                              float* __restrict__ block_sq) {
   __shared__ float lds[256 / WAVE];
   float acc = 0.f;
   for (int ci = blockIdx.x; ci < n_chunks; ci += gridDim.x) {
@@ -52,7 +52,10 @@ __global__ void l2norm_kernel(const float* const* __restrict__ ptrs, const long*
     for (long i = base + threadIdx.x; i < end; i += blockDim.x) acc += p[i] * p[i];
   }
   float s = block_reduce_sum<256>(acc, lds);
-  if (threadIdx.x == 0) atomicAdd(out_sq, s);
+  // one partial per block, summed afterwards in a fixed order: a float
+  // atomicAdd here made the norm (and so the clip factor on every gradient)
+  // depend on block scheduling from run to run
+  if (threadIdx.x == 0) block_sq[blockIdx.x] = s;
 }
 
 // host-side chunk-table builder: returns (meta_tensor_device, chunks_device, n_chunks)
@@ -100,7 +103,6 @@ void multi_tensor_adamw(std::vector<torch::Tensor> params, std::vector<torch::Te
 torch::Tensor multi_tensor_l2norm(std::vector<torch::Tensor> tensors) {
   int n = tensors.size();
   auto dev = tensors[0].device();
-  auto out = torch::zeros({}, torch::TensorOptions().dtype(torch::kFloat32).device(dev));
   std::vector<const float*> ptrs(n);
   std::vector<long> lens(n);
   std::vector<torch::Tensor> keep;
@@ -116,10 +118,12 @@ torch::Tensor multi_tensor_l2norm(std::vector<torch::Tensor> tensors) {
   auto ptr_dev = ptr_cpu.to(dev, true);
   auto len_dev = len_cpu.to(dev, true);
   auto [chunks_dev, n_chunks] = build_chunks(lens, dev);
+  if (n_chunks == 0) return torch::zeros({}, torch::TensorOptions().dtype(torch::kFloat32).device(dev));
   int grid = std::min(n_chunks, 2048);
+  auto out = torch::empty({grid}, torch::TensorOptions().dtype(torch::kFloat32).device(dev));
   auto stream = at::cuda::getCurrentHIPStream();
   hipLaunchKernelGGL(l2norm_kernel, dim3(grid), dim3(256), 0, stream,
                      (const float* const*)ptr_dev.data_ptr(), len_dev.data_ptr<long>(),
                      (const int2*)chunks_dev.data_ptr(), n_chunks, out.data_ptr<float>());
-  return out.sqrt();
+  return out.sum().sqrt();
 }

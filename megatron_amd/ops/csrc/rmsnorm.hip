@@ -46,15 +46,17 @@ __global__ void rmsnorm_fwd_kernel(
 // backward:
 //   dx = rstd * dy*w - x * rstd^3 / H * sum(dy*w*x)
 //   dw = sum_rows dy * (x * rstd)
-// Each block owns a row range; dw accumulated in LDS fp32 then one atomic
-// pass (grid is capped so contention is ~n_blocks per element).
+// Each block owns a row range; dw accumulated in LDS fp32, then written as
+// that block's row of a [n_blocks, H] partial buffer which the host wrapper
+// sums in a fixed order (float atomics would make dw depend on block
+// scheduling from run to run).
 // ---------------------------------------------------------------------------
 
 template <int BLOCK>
 __global__ void rmsnorm_bwd_kernel(
     const short8* __restrict__ dy, const short8* __restrict__ x,
     const short8* __restrict__ w, const float* __restrict__ rstd,
-    short8* __restrict__ dx, float* __restrict__ dw,
+    short8* __restrict__ dx, float* __restrict__ dw_part,
     int rows, int h8) {
   extern __shared__ float smem[];           // [h8*8] fp32 dw accum
   __shared__ float lds[BLOCK / WAVE];
@@ -90,9 +92,8 @@ __global__ void rmsnorm_bwd_kernel(
     }
     __syncthreads();
   }
-  for (int i = threadIdx.x; i < H; i += BLOCK) {
-    if (dw_acc[i] != 0.f) atomicAdd(&dw[i], dw_acc[i]);
-  }
+  float* dw_row = dw_part + (long)blockIdx.x * H;
+  for (int i = threadIdx.x; i < H; i += BLOCK) dw_row[i] = dw_acc[i];
 }
 
 // ---------------------------------------------------------------------------
@@ -123,14 +124,14 @@ std::vector<torch::Tensor> rmsnorm_bwd(torch::Tensor dy, torch::Tensor x, torch:
   auto wc = w.contiguous();
   int rows = x.size(0), h8 = x.size(1) / 8;
   auto dx = torch::empty_like(xc);
-  auto dw32 = torch::zeros({x.size(1)}, x.options().dtype(torch::kFloat32));
   constexpr int BLOCK = 256;
   int grid = std::min(rows, 512);
+  auto dw_part = torch::empty({grid, x.size(1)}, x.options().dtype(torch::kFloat32));
   size_t smem = (size_t)h8 * 8 * sizeof(float);
   auto stream = at::cuda::getCurrentHIPStream();
   hipLaunchKernelGGL((rmsnorm_bwd_kernel<BLOCK>), dim3(grid), dim3(BLOCK), smem, stream,
                      (const short8*)dyc.data_ptr(), (const short8*)xc.data_ptr(),
                      (const short8*)wc.data_ptr(), rstd.data_ptr<float>(),
-                     (short8*)dx.data_ptr(), dw32.data_ptr<float>(), rows, h8);
-  return {dx, dw32.to(torch::kBFloat16)};
+                     (short8*)dx.data_ptr(), dw_part.data_ptr<float>(), rows, h8);
+  return {dx, dw_part.sum(0).to(torch::kBFloat16)};
 }

@@ -309,3 +309,42 @@ def test_bench_model_catalog_shapes():
     assert (m70["num_layers"], m70["hidden_size"]) == (80, 8192)
     mx = bench.MODELS["mixtral-8x7b"]
     assert mx["num_experts"] == 8 and mx["moe_router_topk"] == 2
+
+
+def test_bench_dump_outputs_repeatable(tmp_path):
+    """bench.py --dump-outputs: --steps sets the timed step count, the result
+    line carries ms_per_step, and two runs with the same arguments write the
+    same float32/float64 arrays (seeded inputs).  Tiny model on the CPU path
+    so the comparison is exact."""
+    import subprocess
+    import sys
+
+    import numpy as np
+
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = dict(os.environ, PYTHONPATH=root, HIP_VISIBLE_DEVICES="", CUDA_VISIBLE_DEVICES="")
+    env.pop("RANK", None)
+    env.pop("WORLD_SIZE", None)
+
+    def run(out_dir, *extra):
+        r = subprocess.run(
+            [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "2",
+             "--warmup", "1", "--model", "tiny", "--seq-len", "32", "--micro-batch-size", "1",
+             "--grad-accum", "1", "--dump-outputs", str(out_dir), *extra],
+            cwd=str(tmp_path), env=env, capture_output=True, text=True, timeout=300)
+        assert r.returncode == 0, r.stderr[-2000:]
+        line = json.loads(r.stdout.strip().splitlines()[-1])
+        assert line["steps"] == 2 and line["ms_per_step"] > 0
+        for key in ("metric", "value", "unit", "higher_is_better", "dtype"):
+            assert key in line
+        return {f: np.load(os.path.join(out_dir, f)) for f in sorted(os.listdir(out_dir))}
+
+    a = run(tmp_path / "a")
+    b = run(tmp_path / "b", "--full")
+    assert {"loss.npy", "params_sample.npy", "main_grad_sample.npy"} <= set(a)
+    assert set(a) == set(b)
+    for name, arr in a.items():
+        assert arr.dtype in (np.float32, np.float64), name
+        assert np.isfinite(arr).all(), name
+        assert np.array_equal(arr, b[name]), name
+    assert sum(arr.nbytes for arr in a.values()) <= 64 * 2**20

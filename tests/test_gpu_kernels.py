@@ -72,6 +72,22 @@ def test_rope_fwd_bwd(s, b, h, d):
     assert _rel_err(x.grad, x2.grad) < 2e-2
 
 
+def test_rope_per_step_tables_do_not_share_cos_sin():
+    """Inference gathers a fresh [s, d/2] table per step; each is freed before
+    the next is built, so the allocator reuses its address.  Every step must
+    still rotate by its own positions (same bound as test_rope_fwd_bwd)."""
+    torch.manual_seed(0)
+    s, d = 16, 64
+    x = torch.randn(s, 1, 4, d, device="cuda", dtype=torch.bfloat16)
+    table = ref.rope_freqs(4 * s, d, base=10000.0, device="cuda")
+    for step in range(4):
+        freqs = table[torch.arange(step * s, (step + 1) * s, device="cuda")]
+        out = ops.rope_apply(x, freqs)
+        out_ref = ref.rope_apply(x.float(), freqs)
+        assert _rel_err(out, out_ref) < 2e-2, f"step {step}"
+        del freqs, out, out_ref
+
+
 @pytest.mark.parametrize(
     "sq,skv,b,hq,hkv,causal,window",
     [
@@ -157,6 +173,33 @@ def test_multi_tensor_l2norm():
     n = ops._C.multi_tensor_l2norm([t.flatten() for t in ts])
     expect = torch.sqrt(sum(t.float().pow(2).sum() for t in ts))
     assert abs(n.item() - expect.item()) / expect.item() < 1e-5
+
+
+@pytest.mark.parametrize("numel", [40 * 65536 + 5, 2100 * 65536 + 5])  # many blocks; past the 2048-block grid cap
+def test_multi_tensor_l2norm_repeats_bitwise(numel):
+    """The clip factor scales every gradient, so the norm must not depend on
+    block scheduling: per-block partials are summed in a fixed order."""
+    torch.manual_seed(0)
+    ts = [torch.randn(numel, device="cuda"), torch.randn(997, device="cuda")]
+    expect = torch.sqrt(sum(t.double().pow(2).sum() for t in ts)).item()
+    norms = [ops._C.multi_tensor_l2norm(ts).item() for _ in range(5)]
+    assert abs(norms[0] - expect) / expect < 1e-5
+    assert all(n == norms[0] for n in norms)
+
+
+def test_rmsnorm_bwd_dw_repeats_bitwise():
+    """dw is reduced over row blocks in a fixed order (512 blocks here, each
+    owning several rows): repeated calls give the same bits."""
+    torch.manual_seed(0)
+    rows, h = 2048 + 33, 1024
+    x = torch.randn(rows, h, device="cuda", dtype=torch.bfloat16)
+    w = torch.randn(h, device="cuda", dtype=torch.bfloat16)
+    dy = torch.randn(rows, h, device="cuda", dtype=torch.bfloat16)
+    _, rstd = ops._C.rmsnorm_fwd(x, w, 1e-5)
+    first = ops._C.rmsnorm_bwd(dy, x, w, rstd)
+    for _ in range(4):
+        dx, dw = ops._C.rmsnorm_bwd(dy, x, w, rstd)
+        assert torch.equal(dx, first[0]) and torch.equal(dw, first[1])
 
 
 def test_model_smoke_bf16():
