@@ -1,30 +1,133 @@
 // Fused attention BACKWARD for CDNA4 (K1).  Atomic-free two-kernel split
 // (the FA2-style trade: P/dS recomputed in both kernels, no dq atomics):
-//   bwd_dq :  block per (128 q rows, b*hq)  — dq = dS K
+//   bwd_dq :  block per (128 or 256 q rows, b*hq)  — dq = dS K
 //   bwd_dkv:  block per (128 kv rows, b*hkv), q-heads of the GQA group looped
 //             inside — dv = P^T dO ; dk = dS^T Q
 // plus a rowsum preprocess  Drow = sum_d(dO * O).
 //
-// v2 structure (same technique stack as attention_fwd v2):
-//   * swapped-operand MFMAs so every LDS operand is consumed as an A-fragment
-//     of a row-major tile; the P/dS D-fragment -> A-fragment relayout is two
-//     register-pair permlane swaps (dfrag_to_at, common.h) - no LDS round-trip.
-//   * single-staged swizzled LDS tiles per iteration tile, reg-staged
-//     issue-early/write-late prefetch (T14), two barriers per tile.
-//   * separate staging lane maps: row-linear (coalesced) for row-major
-//     buffers, kv-fast for transposed buffers (bank-spread scalar stores).
+// Structure (v4):
+//   * swapped-operand phase-1 MFMAs: every LDS tile is consumed as an
+//     A-fragment of a row-major tile.  Which tile row feeds which MFMA row
+//     is free, so sub-tile n feeds MFMA row i with tile row
+//     32(n>>1) + 8(i>>2) + 4(n&1) + (i&3)  (tile_row_a).  The D-fragment of
+//     lane (g,c) then holds column c at tile rows 32(n>>1)+8g+4(n&1)+r
+//     (tile_row_d): over the sub-tile pair (2ks, 2ks+1) exactly the rows
+//     32ks+8g..+7, in order - the A-fragment of the phase-2 MFMA with the
+//     natural k order, without any cross-lane relayout.  The matching
+//     B-fragment is read from the SAME row-major tile with the transposing
+//     LDS read (ds_read_b64_tr_b16), so no transposed copy of any tile
+//     exists, in LDS or in registers.  Every MFMA sees the same operands in
+//     the same k slots as with transposed tiles and a permlane relayout, so
+//     results are bit-identical to that formulation.
+//   * double-buffered swizzled LDS tiles, reg-staged issue-early/write-late
+//     prefetch (T14), ONE barrier per tile.  Each block is alone on its CU
+//     (512 threads at 2 waves/SIMD), so the barrier count is what it hides
+//     least well.
+//   * wave-uniform interior-tile path with no mask arithmetic; only tiles on
+//     the diagonal, the window edge or the ragged tail evaluate the mask.
 //   * per-wave causal/window tile skip; scale folded into one fma per exp.
 #include <torch/extension.h>
 #include <ATen/hip/HIPContext.h>
+#include <type_traits>
 #include "common.h"
 
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
+typedef short short4v __attribute__((ext_vector_type(4)));
 
 #define LOG2E 1.44269504088896340736f
 #define WAIT_VM0 0x0F70
 
-__device__ __forceinline__ int swzb(int row, int chunk) { return chunk ^ (row & 7); }
+// 16-byte chunk swizzle of a row-major [rows][D] bf16 tile: chunk ^ swzf(row).
+// LDS has 64 four-byte banks, so 256 B (one D=128 row, two D=64 rows) is one
+// pass over the banks.  The term is chosen so that both read patterns of a
+// tile touch every bank once per pass.  Write a row as 16A + 8a + 4h + e
+// (e = row & 3, h = bit 2, a = bit 3, A = bit 4; h is the same for all
+// lanes of either read):
+//   * phase 1, b128: 16 lanes read the same logical chunk of the rows
+//     (A, a, e) = all 16 combinations -> the term (D = 128) resp. the term
+//     together with the row parity (D = 64) must differ for all of them;
+//   * phase 2, transposing b64: 32 lanes read one 32-byte chunk pair of the
+//     rows (a, e) = all 8 combinations at fixed A -> bits 1.. of the term
+//     (with the row parity for D = 64) must differ for all of them.
+template <int D>
+__device__ __forceinline__ int swzf(int row) {
+  const int lo = (D == 128) ? (row & 3) : ((row >> 1) & 1);
+  return (lo << 2) | (((row >> 3) & 1) << 1) | ((row >> 4) & 1);
+}
+template <int D>
+__device__ __forceinline__ int swz(int row, int chunk) { return chunk ^ swzf<D>(row); }
+
+// Transposing LDS read.  Within each group of 16 lanes, lane i supplies the
+// address of 4 consecutive bf16: row i>>2, columns 4(i&3)..+3 of a 4x16
+// block; lane c receives column c of that block (4 rows).
+__device__ __forceinline__ short4v lds_read_tr(const char* p) {
+  return __builtin_amdgcn_ds_read_tr16_b64_v4i16(
+      (__attribute__((address_space(3))) short4v*)(p));
+}
+
+// Tile row that sub-tile n feeds into MFMA row i in phase 1, and tile row of
+// element r of lane group g's D-fragment of sub-tile n (see top of file).
+__device__ __forceinline__ int tile_row_a(int n, int i) {
+  return 32 * (n >> 1) + 8 * (i >> 2) + 4 * (n & 1) + (i & 3);
+}
+__device__ __forceinline__ int tile_row_d(int n, int g, int r) {
+  return 32 * (n >> 1) + 8 * g + 4 * (n & 1) + r;
+}
+
+// Lane-constant byte offset of this lane's share of a transposed read of rows
+// 8g..8g+3 (relative to a 32-row-aligned base) and the 16 columns of d-block 0.
+template <int D>
+__device__ __forceinline__ int tr_lane_base(int g, int c) {
+  const int row = 8 * g + (c >> 2), sub = c & 3;
+  return row * (2 * D) + ((((sub >> 1) ^ swzf<D>(row)) << 4) | ((sub & 1) << 3));
+}
+
+// B-fragment of a phase-2 MFMA for d-block nd, reduction rows r32..r32+31 of
+// a swizzled row-major tile in the natural k order: lane group g gets rows
+// r32+8g..+7 as two 4-row transposed reads.  swzf ignores row bits 2 and 5
+// and d-block nd moves the chunk index by 2nd, which commutes with the
+// swizzle xor: one v_xor per fragment, the rest is an immediate offset.
+template <int D>
+__device__ __forceinline__ bf16x8 read_b_tr(const short* tile, int lane_base, int r32, int nd) {
+  const char* p = reinterpret_cast<const char*>(tile) + (lane_base ^ (nd * 32));
+  short4v lo = lds_read_tr(p + r32 * (2 * D));
+  short4v hi = lds_read_tr(p + (r32 + 4) * (2 * D));
+  short8 t = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
+  return *reinterpret_cast<bf16x8*>(&t);
+}
+
+// A-fragment made of the lane's own packed D-fragments (no relayout).
+__device__ __forceinline__ bf16x8 own_a_frag(const int lo[2], const int hi[2]) {
+  int4 a = make_int4(lo[0], lo[1], hi[0], hi[1]);
+  return *reinterpret_cast<bf16x8*>(&a);
+}
+
+// Broadcast lane I of each row of 16 lanes to the whole row (DPP, no LDS).
+template <int I>
+__device__ __forceinline__ float row_bcast_i(float v) {
+  return __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, v), 0x150 + I, 0xf, 0xf, false));
+}
+__device__ __forceinline__ float row_bcast(float v, int i) {
+  switch (i) {
+    case 0: return row_bcast_i<0>(v);
+    case 1: return row_bcast_i<1>(v);
+    case 2: return row_bcast_i<2>(v);
+    case 3: return row_bcast_i<3>(v);
+    case 4: return row_bcast_i<4>(v);
+    case 5: return row_bcast_i<5>(v);
+    case 6: return row_bcast_i<6>(v);
+    case 7: return row_bcast_i<7>(v);
+    case 8: return row_bcast_i<8>(v);
+    case 9: return row_bcast_i<9>(v);
+    case 10: return row_bcast_i<10>(v);
+    case 11: return row_bcast_i<11>(v);
+    case 12: return row_bcast_i<12>(v);
+    case 13: return row_bcast_i<13>(v);
+    case 14: return row_bcast_i<14>(v);
+    default: return row_bcast_i<15>(v);
+  }
+}
 
 // ---------------------------------------------------------------------------
 // Drow[b, h, s] = sum_d dO[s,b,h,:] * O[s,b,h,:]
@@ -52,29 +155,31 @@ __global__ void attn_bwd_rowsum_kernel(const short8* __restrict__ dout, const sh
 }
 
 // ---------------------------------------------------------------------------
-// dq kernel: 8 waves, 128 q rows per block (16 per wave), kv tiles of 64.
+// dq kernel: 8 waves x 16*QT q rows (QT = 2: 256-row blocks, every K/V
+// A-fragment read feeds two MFMAs; QT = 1: 128-row blocks for short
+// sequences and D = 64), kv tiles of 64.
 //   ST  = mfma(A=K_lds,  B=Q_regs)   D[kv][q]
 //   dPT = mfma(A=V_lds,  B=dO_regs)  D[kv][q]
-//   dq += mfma(A=dS_frag(permlane),  B=Kt_lds)
+//   dq += mfma(A=dS (own D-fragments),  B=K_lds via transposing read)
 // ---------------------------------------------------------------------------
-template <int D>
+template <int D, int QT>
 __global__ __launch_bounds__(512) void attn_bwd_dq_kernel(
     const bf16* __restrict__ q, const bf16* __restrict__ k, const bf16* __restrict__ v,
     const bf16* __restrict__ dout, const float* __restrict__ lse, const float* __restrict__ drow,
     bf16* __restrict__ dq,
     int sq, int skv, int b, int hq, int hkv, float scale, int causal, int window) {
   constexpr int KVBLK = 64;
+  constexpr int QROWS = 16 * QT;  // q rows per wave
   constexpr int ND = D / 16, NKD = D / 32;
   constexpr int KCH = D / 8;
   constexpr int SREG = KVBLK * D / 8 / 512;
 
-  __shared__ __align__(16) short K_lds[KVBLK][D];   // row-major, swizzled
-  __shared__ __align__(16) short V_lds[KVBLK][D];   // row-major, swizzled
-  __shared__ __align__(16) short Kt_lds[D][KVBLK];  // transposed, swizzled
+  __shared__ __align__(16) short K_lds[2][KVBLK][D];  // row-major, swizzled, double-buffered
+  __shared__ __align__(16) short V_lds[2][KVBLK][D];
 
   const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
   const int g = lane >> 4, c = lane & 15;
-  const int q0 = blockIdx.x * 128;
+  const int q0 = blockIdx.x * (8 * QROWS);
   const int batch = blockIdx.y / hq, head = blockIdx.y % hq;
   const int kv_head = head / (hq / hkv);
   const long q_srow = (long)b * hq * D, k_srow = (long)b * hkv * D;
@@ -86,170 +191,187 @@ __global__ __launch_bounds__(512) void attn_bwd_dq_kernel(
   const float* lse_row = lse + ((long)batch * hq + head) * sq;
   const float* dr_row = drow + ((long)batch * hq + head) * sq;
 
-  const int row0 = q0 + wid * 16;
+  const int row0 = q0 + wid * QROWS;
   const int off = skv - sq;
+  const int trb = tr_lane_base<D>(g, c);
 
-  bf16x8 qa[NKD], doa[NKD];
-  {
-    int qrow = min(row0 + c, sq - 1);
+  bf16x8 qa[QT][NKD], doa[QT][NKD];
+  float my_lse_l2[QT], my_dr_s[QT];
+#pragma unroll
+  for (int qt = 0; qt < QT; ++qt) {
+    int qrow = min(row0 + qt * 16 + c, sq - 1);
     const bf16* qr = qbase + (long)qrow * q_srow;
     const bf16* dor = dobase + (long)qrow * q_srow;
 #pragma unroll
     for (int kd = 0; kd < NKD; ++kd) {
       short8 t1 = *reinterpret_cast<const short8*>(qr + kd * 32 + g * 8);
-      qa[kd] = *reinterpret_cast<bf16x8*>(&t1);
+      qa[qt][kd] = *reinterpret_cast<bf16x8*>(&t1);
       short8 t2 = *reinterpret_cast<const short8*>(dor + kd * 32 + g * 8);
-      doa[kd] = *reinterpret_cast<bf16x8*>(&t2);
+      doa[qt][kd] = *reinterpret_cast<bf16x8*>(&t2);
     }
+    my_lse_l2[qt] = lse_row[qrow] * LOG2E;
+    my_dr_s[qt] = dr_row[qrow] * scale;
   }
   const float c1 = scale * LOG2E;
-  const float my_lse_l2 = lse_row[min(row0 + c, sq - 1)] * LOG2E;
-  const float my_dr_s = dr_row[min(row0 + c, sq - 1)] * scale;
 
-  f32x4 dq_acc[ND];
+  f32x4 dq_acc[QT][ND];
 #pragma unroll
-  for (int n = 0; n < ND; ++n) dq_acc[n] = f32x4{0.f, 0.f, 0.f, 0.f};
+  for (int qt = 0; qt < QT; ++qt)
+#pragma unroll
+    for (int n = 0; n < ND; ++n) dq_acc[qt][n] = f32x4{0.f, 0.f, 0.f, 0.f};
 
-  int t_end = causal ? min((q0 + 127 + off) / KVBLK, (skv - 1) / KVBLK) : (skv - 1) / KVBLK;
+  int t_end = causal ? min((q0 + 8 * QROWS - 1 + off) / KVBLK, (skv - 1) / KVBLK) : (skv - 1) / KVBLK;
   int t_start = (window > 0) ? max(0, (q0 + off - window + 1) / KVBLK) : 0;
 
-  int st_row[SREG], st_c8[SREG], sv_row[SREG], sv_c8[SREG];
+  int st_row[SREG], st_c8[SREG];
 #pragma unroll
   for (int i = 0; i < SREG; ++i) {
     int idx = (int)threadIdx.x + i * 512;
     st_row[i] = idx / KCH;
     st_c8[i] = idx % KCH;
-    sv_row[i] = idx & (KVBLK - 1);
-    sv_c8[i] = idx / KVBLK;
   }
 
-  short8 kreg[SREG], vreg[SREG], ktreg[SREG];
+  short8 kreg[SREG], vreg[SREG];
   auto stage_loads = [&](int k0) {
 #pragma unroll
     for (int i = 0; i < SREG; ++i) {
       int krow = k0 + st_row[i];
       kreg[i] = short8{0, 0, 0, 0, 0, 0, 0, 0};
       vreg[i] = short8{0, 0, 0, 0, 0, 0, 0, 0};
-      ktreg[i] = short8{0, 0, 0, 0, 0, 0, 0, 0};
       if (krow < skv) {
         kreg[i] = *reinterpret_cast<const short8*>(kbase + (long)krow * k_srow + st_c8[i] * 8);
         vreg[i] = *reinterpret_cast<const short8*>(vbase + (long)krow * k_srow + st_c8[i] * 8);
       }
-      int trow = k0 + sv_row[i];
-      if (trow < skv)
-        ktreg[i] = *reinterpret_cast<const short8*>(kbase + (long)trow * k_srow + sv_c8[i] * 8);
     }
   };
-  auto stage_writes = [&]() {
+  auto stage_writes = [&](int buf) {
 #pragma unroll
     for (int i = 0; i < SREG; ++i) {
-      *reinterpret_cast<short8*>(&K_lds[st_row[i]][swzb(st_row[i], st_c8[i]) * 8]) = kreg[i];
-      *reinterpret_cast<short8*>(&V_lds[st_row[i]][swzb(st_row[i], st_c8[i]) * 8]) = vreg[i];
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        int d = sv_c8[i] * 8 + j;
-        Kt_lds[d][swzb(d, sv_row[i] >> 3) * 8 + (sv_row[i] & 7)] = ktreg[i][j];
-      }
+      *reinterpret_cast<short8*>(&K_lds[buf][st_row[i]][swz<D>(st_row[i], st_c8[i]) * 8]) = kreg[i];
+      *reinterpret_cast<short8*>(&V_lds[buf][st_row[i]][swz<D>(st_row[i], st_c8[i]) * 8]) = vreg[i];
     }
   };
 
   stage_loads(t_start * KVBLK);
-  stage_writes();
+  stage_writes(0);
   __syncthreads();
 
   for (int t = t_start; t <= t_end; ++t) {
     const int k0 = t * KVBLK;
+    const int cur = (t - t_start) & 1;
     const bool have_next = (t + 1 <= t_end);
     if (have_next) stage_loads(k0 + KVBLK);
 
-    bool wave_skip = (causal && k0 > row0 + 15 + off) ||
+    bool wave_skip = (causal && k0 > row0 + QROWS - 1 + off) ||
                      (window > 0 && k0 + KVBLK - 1 < row0 + off - window + 1);
     if (!wave_skip) {
-      f32x4 st[KVBLK / 16], dpt[KVBLK / 16];
-      __builtin_amdgcn_s_setprio(1);
+      // no element of this wave's (q rows) x (kv tile) needs the mask
+      const bool interior = (k0 + KVBLK <= skv) && (row0 + QROWS <= sq) &&
+                            (!causal || k0 + KVBLK - 1 <= row0 + off) &&
+                            (window <= 0 || k0 > row0 + QROWS - 1 + off - window);
+      // per 16-row kv sub-tile: S^T/dP^T MFMAs -> dS -> packed pairs
+      int pk[KVBLK / 16][QT][2];  // [n][qt][pair]
+      auto phase1 = [&](auto masked_c) {
+        constexpr bool MASKED = decltype(masked_c)::value;
+        __builtin_amdgcn_s_setprio(1);
 #pragma unroll
-      for (int n = 0; n < KVBLK / 16; ++n) {
-        st[n] = f32x4{0.f, 0.f, 0.f, 0.f};
-        dpt[n] = f32x4{0.f, 0.f, 0.f, 0.f};
-        int krow = n * 16 + c;
+        for (int n = 0; n < KVBLK / 16; ++n) {
+          f32x4 st[QT], dpt[QT];
 #pragma unroll
-        for (int kd = 0; kd < NKD; ++kd) {
-          short8 t1 = *reinterpret_cast<const short8*>(&K_lds[krow][swzb(krow, kd * 4 + g) * 8]);
-          bf16x8 ak = *reinterpret_cast<bf16x8*>(&t1);
-          short8 t2 = *reinterpret_cast<const short8*>(&V_lds[krow][swzb(krow, kd * 4 + g) * 8]);
-          bf16x8 av = *reinterpret_cast<bf16x8*>(&t2);
-          st[n] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ak, qa[kd], st[n], 0, 0, 0);
-          dpt[n] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(av, doa[kd], dpt[n], 0, 0, 0);
+          for (int qt = 0; qt < QT; ++qt) {
+            st[qt] = f32x4{0.f, 0.f, 0.f, 0.f};
+            dpt[qt] = f32x4{0.f, 0.f, 0.f, 0.f};
+          }
+          int krow = tile_row_a(n, c);
+#pragma unroll
+          for (int kd = 0; kd < NKD; ++kd) {
+            short8 t1 = *reinterpret_cast<const short8*>(&K_lds[cur][krow][swz<D>(krow, kd * 4 + g) * 8]);
+            bf16x8 ak = *reinterpret_cast<bf16x8*>(&t1);
+            short8 t2 = *reinterpret_cast<const short8*>(&V_lds[cur][krow][swz<D>(krow, kd * 4 + g) * 8]);
+            bf16x8 av = *reinterpret_cast<bf16x8*>(&t2);
+#pragma unroll
+            for (int qt = 0; qt < QT; ++qt) {
+              st[qt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ak, qa[qt][kd], st[qt], 0, 0, 0);
+              dpt[qt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(av, doa[qt][kd], dpt[qt], 0, 0, 0);
+            }
+          }
+          // P, dS in D-layout [kv = tile_row_d(n, g, r)][q = c]; pack dS pairs along kv
+#pragma unroll
+          for (int qt = 0; qt < QT; ++qt) {
+            const int qrow = row0 + qt * 16 + c;
+            float ds[4];
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+              float pt = exp2f(__builtin_fmaf(st[qt][r], c1, -my_lse_l2[qt]));
+              if constexpr (MASKED) {
+                int kvrow = k0 + tile_row_d(n, g, r);
+                bool ok = (kvrow < skv) && (qrow < sq);
+                if (causal) ok &= (kvrow <= qrow + off);
+                if (window > 0) ok &= (kvrow > qrow + off - window);
+                pt = ok ? pt : 0.f;
+              }
+              ds[r] = pt * __builtin_fmaf(dpt[qt][r], scale, -my_dr_s[qt]);
+            }
+            pk[n][qt][0] = pack_bf16x2(ds[0], ds[1]);
+            pk[n][qt][1] = pack_bf16x2(ds[2], ds[3]);
+          }
         }
-      }
-      __builtin_amdgcn_s_setprio(0);
+      };
+      if (interior) phase1(std::false_type{});
+      else phase1(std::true_type{});
+      __builtin_amdgcn_sched_barrier(0);
 
-      // P, dS in D-layout [kv = g*4+r][q = c]; pack dS pairs along kv
-      int pk[KVBLK / 16][2];
-      const int qrow = row0 + c;
-#pragma unroll
-      for (int n = 0; n < KVBLK / 16; ++n) {
-        float ds[4];
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          int kvrow = k0 + n * 16 + g * 4 + r;
-          bool ok = (kvrow < skv) && (qrow < sq);
-          if (causal) ok &= (kvrow <= qrow + off);
-          if (window > 0) ok &= (kvrow > qrow + off - window);
-          float pt = ok ? exp2f(__builtin_fmaf(st[n][r], c1, -my_lse_l2)) : 0.f;
-          ds[r] = pt * __builtin_fmaf(dpt[n][r], scale, -my_dr_s);
-        }
-        pk[n][0] = pack_bf16x2(ds[0], ds[1]);
-        pk[n][1] = pack_bf16x2(ds[2], ds[3]);
-      }
-
-      // dq += dS K : A = dS[q][kv] (permlane relayout), B = Kt
-      __builtin_amdgcn_s_setprio(1);
+      // dq += dS K : one transposed K read feeds all QT MFMAs
 #pragma unroll
       for (int ks2 = 0; ks2 < KVBLK / 32; ++ks2) {
-        int av4[4];
-        dfrag_to_at(pk[2 * ks2], pk[2 * ks2 + 1], av4);
-        int4 av = make_int4(av4[0], av4[1], av4[2], av4[3]);
-        bf16x8 a = *reinterpret_cast<bf16x8*>(&av);
+        bf16x8 a[QT];
+#pragma unroll
+        for (int qt = 0; qt < QT; ++qt) a[qt] = own_a_frag(pk[2 * ks2][qt], pk[2 * ks2 + 1][qt]);
 #pragma unroll
         for (int n = 0; n < ND; ++n) {
-          int vrow = n * 16 + c;
-          short8 t3 = *reinterpret_cast<const short8*>(&Kt_lds[vrow][swzb(vrow, ks2 * 4 + g) * 8]);
-          bf16x8 bK = *reinterpret_cast<bf16x8*>(&t3);
-          dq_acc[n] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, bK, dq_acc[n], 0, 0, 0);
+          bf16x8 bK = read_b_tr<D>(&K_lds[cur][0][0], trb, ks2 * 32, n);
+#pragma unroll
+          for (int qt = 0; qt < QT; ++qt)
+            dq_acc[qt][n] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[qt], bK, dq_acc[qt][n], 0, 0, 0);
         }
       }
       __builtin_amdgcn_s_setprio(0);
     }
 
     if (have_next) {
-      __syncthreads();
+      // the other buffer was last read in iteration t-1, before that
+      // iteration's barrier
       __builtin_amdgcn_s_waitcnt(WAIT_VM0);
       __builtin_amdgcn_sched_barrier(0);
-      stage_writes();
+      stage_writes(cur ^ 1);
       __syncthreads();
     }
   }
 
 #pragma unroll
-  for (int r = 0; r < 4; ++r) {
-    int row = row0 + g * 4 + r;
-    if (row >= sq) continue;
-    bf16* dqr = dqbase + (long)row * q_srow;
+  for (int qt = 0; qt < QT; ++qt)
 #pragma unroll
-    for (int n = 0; n < ND; ++n) dqr[n * 16 + c] = f2bf(dq_acc[n][r]);
-  }
+    for (int r = 0; r < 4; ++r) {
+      int row = row0 + qt * 16 + g * 4 + r;
+      if (row >= sq) continue;
+      bf16* dqr = dqbase + (long)row * q_srow;
+#pragma unroll
+      for (int n = 0; n < ND; ++n) dqr[n * 16 + c] = f2bf(dq_acc[qt][n][r]);
+    }
 }
 
 // ---------------------------------------------------------------------------
 // dk/dv kernel: 8 waves, 128 kv rows per block (16 per wave), q tiles of 64.
 //   S  = mfma(A=Q_lds,  B=K_regs)   D[q][kv]
 //   dP = mfma(A=dO_lds, B=V_regs)   D[q][kv]
-//   dV += mfma(A=P^T_frag(permlane),  B=dOt_lds)
-//   dK += mfma(A=dS^T_frag(permlane), B=Qt_lds)
+//   dV += mfma(A=P^T  (own D-fragments), B=dO_lds via transposing read)
+//   dK += mfma(A=dS^T (own D-fragments), B=Q_lds  via transposing read)
+// lse/drow of the q tile never touch LDS: lane (g,c) loads the tile row
+// tile_row_d(c>>2, g, c&3), so the 16 rows a lane group needs sit in its own
+// row of 16 lanes and are fetched with DPP row broadcasts.
 // ---------------------------------------------------------------------------
 template <int D>
-__global__ __launch_bounds__(512, 2) void attn_bwd_dkv_kernel(
+__global__ __launch_bounds__(512) void attn_bwd_dkv_kernel(
     const bf16* __restrict__ q, const bf16* __restrict__ k, const bf16* __restrict__ v,
     const bf16* __restrict__ dout, const float* __restrict__ lse, const float* __restrict__ drow,
     bf16* __restrict__ dk, bf16* __restrict__ dv,
@@ -259,12 +381,8 @@ __global__ __launch_bounds__(512, 2) void attn_bwd_dkv_kernel(
   constexpr int KCH = D / 8;
   constexpr int SREG = QBLK * D / 8 / 512;
 
-  __shared__ __align__(16) short Q_lds[QBLK][D];
-  __shared__ __align__(16) short dO_lds[QBLK][D];
-  __shared__ __align__(16) short Qt_lds[D][QBLK];
-  __shared__ __align__(16) short dOt_lds[D][QBLK];
-  __shared__ float lse_s[QBLK];   // lse * LOG2E for the staged q tile
-  __shared__ float dr_s[QBLK];    // drow * scale
+  __shared__ __align__(16) short Q_lds[2][QBLK][D];   // row-major, swizzled, double-buffered
+  __shared__ __align__(16) short dO_lds[2][QBLK][D];
 
   const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
   const int g = lane >> 4, c = lane & 15;
@@ -280,6 +398,8 @@ __global__ __launch_bounds__(512, 2) void attn_bwd_dkv_kernel(
   const int krow0 = k0 + wid * 16;
   const int off = skv - sq;
   const float c1 = scale * LOG2E;
+  const int trb = tr_lane_base<D>(g, c);
+  const int stat_row = tile_row_d(c >> 2, g, c & 3);  // q-tile row whose lse/drow this lane loads
 
   // K/V B-fragments: lane (g,c) holds row krow0 + c (= B col c)
   bf16x8 ka[NKD], va[NKD];
@@ -307,14 +427,12 @@ __global__ __launch_bounds__(512, 2) void attn_bwd_dkv_kernel(
   int tq_end = (sq - 1) / QBLK;
   if (window > 0) tq_end = min(tq_end, (k0 + 127 - off + window - 1) / QBLK);
 
-  int st_row[SREG], st_c8[SREG], sv_row[SREG], sv_c8[SREG];
+  int st_row[SREG], st_c8[SREG];
 #pragma unroll
   for (int i = 0; i < SREG; ++i) {
     int idx = (int)threadIdx.x + i * 512;
     st_row[i] = idx / KCH;
     st_c8[i] = idx % KCH;
-    sv_row[i] = idx & (QBLK - 1);
-    sv_c8[i] = idx / QBLK;
   }
 
   for (int hg = 0; hg < rep; ++hg) {
@@ -324,51 +442,41 @@ __global__ __launch_bounds__(512, 2) void attn_bwd_dkv_kernel(
     const float* lse_row = lse + ((long)batch * hq + head) * sq;
     const float* dr_row = drow + ((long)batch * hq + head) * sq;
 
-    short8 qrm[SREG], dorm[SREG], qtr[SREG], dotr[SREG];
+    short8 qrm[SREG], dorm[SREG];
+    float lse_nx, dr_nx;        // staged for the next tile
+    float lse_cu = 0.f, dr_cu = 0.f;  // lse * LOG2E, drow * scale of the current tile
     auto stage_loads = [&](int qt0) {
 #pragma unroll
       for (int i = 0; i < SREG; ++i) {
         int r1 = qt0 + st_row[i];
         qrm[i] = short8{0, 0, 0, 0, 0, 0, 0, 0};
         dorm[i] = short8{0, 0, 0, 0, 0, 0, 0, 0};
-        qtr[i] = short8{0, 0, 0, 0, 0, 0, 0, 0};
-        dotr[i] = short8{0, 0, 0, 0, 0, 0, 0, 0};
         if (r1 < sq) {
           qrm[i] = *reinterpret_cast<const short8*>(qbase + (long)r1 * q_srow + st_c8[i] * 8);
           dorm[i] = *reinterpret_cast<const short8*>(dobase + (long)r1 * q_srow + st_c8[i] * 8);
         }
-        int r2 = qt0 + sv_row[i];
-        if (r2 < sq) {
-          qtr[i] = *reinterpret_cast<const short8*>(qbase + (long)r2 * q_srow + sv_c8[i] * 8);
-          dotr[i] = *reinterpret_cast<const short8*>(dobase + (long)r2 * q_srow + sv_c8[i] * 8);
-        }
       }
+      int qi = min(qt0 + stat_row, sq - 1);
+      lse_nx = lse_row[qi];
+      dr_nx = dr_row[qi];
     };
-    auto stage_writes = [&](int qt0) {
+    auto stage_writes = [&](int buf) {
 #pragma unroll
       for (int i = 0; i < SREG; ++i) {
-        *reinterpret_cast<short8*>(&Q_lds[st_row[i]][swzb(st_row[i], st_c8[i]) * 8]) = qrm[i];
-        *reinterpret_cast<short8*>(&dO_lds[st_row[i]][swzb(st_row[i], st_c8[i]) * 8]) = dorm[i];
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-          int d = sv_c8[i] * 8 + j;
-          Qt_lds[d][swzb(d, sv_row[i] >> 3) * 8 + (sv_row[i] & 7)] = qtr[i][j];
-          dOt_lds[d][swzb(d, sv_row[i] >> 3) * 8 + (sv_row[i] & 7)] = dotr[i][j];
-        }
+        *reinterpret_cast<short8*>(&Q_lds[buf][st_row[i]][swz<D>(st_row[i], st_c8[i]) * 8]) = qrm[i];
+        *reinterpret_cast<short8*>(&dO_lds[buf][st_row[i]][swz<D>(st_row[i], st_c8[i]) * 8]) = dorm[i];
       }
-      if (threadIdx.x < QBLK) {
-        int qi = min(qt0 + (int)threadIdx.x, sq - 1);
-        lse_s[threadIdx.x] = lse_row[qi] * LOG2E;
-        dr_s[threadIdx.x] = dr_row[qi] * scale;
-      }
+      lse_cu = lse_nx * LOG2E;
+      dr_cu = dr_nx * scale;
     };
 
     stage_loads(tq_start * QBLK);
-    stage_writes(tq_start * QBLK);
+    stage_writes(0);
     __syncthreads();
 
     for (int t = tq_start; t <= tq_end; ++t) {
       const int qt0 = t * QBLK;
+      const int cur = (t - tq_start) & 1;
       const bool have_next = (t + 1 <= tq_end);
       if (have_next) stage_loads(qt0 + QBLK);
 
@@ -376,18 +484,22 @@ __global__ __launch_bounds__(512, 2) void attn_bwd_dkv_kernel(
       bool wave_skip = (causal && qt0 + QBLK - 1 < krow0 - off) ||
                        (window > 0 && qt0 >= krow0 + 15 - off + window);
       if (!wave_skip) {
+        // no element of this wave's (q tile) x (kv rows) needs the mask
+        const bool interior = (qt0 + QBLK <= sq) && (krow0 + 16 <= skv) &&
+                              (!causal || krow0 + 15 <= qt0 + off) &&
+                              (window <= 0 || krow0 > qt0 + QBLK - 1 + off - window);
         f32x4 st[QBLK / 16], dpt[QBLK / 16];
         __builtin_amdgcn_s_setprio(1);
 #pragma unroll
         for (int n = 0; n < QBLK / 16; ++n) {
           st[n] = f32x4{0.f, 0.f, 0.f, 0.f};
           dpt[n] = f32x4{0.f, 0.f, 0.f, 0.f};
-          int qrow = n * 16 + c;
+          int qrow = tile_row_a(n, c);
 #pragma unroll
           for (int kd = 0; kd < NKD; ++kd) {
-            short8 t1 = *reinterpret_cast<const short8*>(&Q_lds[qrow][swzb(qrow, kd * 4 + g) * 8]);
+            short8 t1 = *reinterpret_cast<const short8*>(&Q_lds[cur][qrow][swz<D>(qrow, kd * 4 + g) * 8]);
             bf16x8 aq = *reinterpret_cast<bf16x8*>(&t1);
-            short8 t2 = *reinterpret_cast<const short8*>(&dO_lds[qrow][swzb(qrow, kd * 4 + g) * 8]);
+            short8 t2 = *reinterpret_cast<const short8*>(&dO_lds[cur][qrow][swz<D>(qrow, kd * 4 + g) * 8]);
             bf16x8 ado = *reinterpret_cast<bf16x8*>(&t2);
             st[n] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(aq, ka[kd], st[n], 0, 0, 0);
             dpt[n] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ado, va[kd], dpt[n], 0, 0, 0);
@@ -395,47 +507,48 @@ __global__ __launch_bounds__(512, 2) void attn_bwd_dkv_kernel(
         }
         __builtin_amdgcn_s_setprio(0);
 
-        // P, dS in D-layout [q = g*4+r][kv = c]; kv col = krow0 + c
+        // P, dS in D-layout [q = tile_row_d(n, g, r)][kv = c]; kv col = krow0 + c
         int pkP[QBLK / 16][2], pkD[QBLK / 16][2];
-        const int kvcol = krow0 + c;
+        auto softmax_tile = [&](auto masked_c) {
+          constexpr bool MASKED = decltype(masked_c)::value;
+          const int kvcol = krow0 + c;
 #pragma unroll
-        for (int n = 0; n < QBLK / 16; ++n) {
-          float pv[4], dsv[4];
+          for (int n = 0; n < QBLK / 16; ++n) {
+            float pv[4], dsv[4];
 #pragma unroll
-          for (int r = 0; r < 4; ++r) {
-            int qi = n * 16 + g * 4 + r;
-            int qrow = qt0 + qi;
-            bool ok = (kvcol < skv) && (qrow < sq);
-            if (causal) ok &= (kvcol <= qrow + off);
-            if (window > 0) ok &= (kvcol > qrow + off - window);
-            float pt = ok ? exp2f(__builtin_fmaf(st[n][r], c1, -lse_s[qi])) : 0.f;
-            pv[r] = pt;
-            dsv[r] = pt * __builtin_fmaf(dpt[n][r], scale, -dr_s[qi]);
+            for (int r = 0; r < 4; ++r) {
+              const float lse_q = row_bcast(lse_cu, 4 * n + r);
+              const float dr_q = row_bcast(dr_cu, 4 * n + r);
+              float pt = exp2f(__builtin_fmaf(st[n][r], c1, -lse_q));
+              if constexpr (MASKED) {
+                int qrow = qt0 + tile_row_d(n, g, r);
+                bool ok = (kvcol < skv) && (qrow < sq);
+                if (causal) ok &= (kvcol <= qrow + off);
+                if (window > 0) ok &= (kvcol > qrow + off - window);
+                pt = ok ? pt : 0.f;
+              }
+              pv[r] = pt;
+              dsv[r] = pt * __builtin_fmaf(dpt[n][r], scale, -dr_q);
+            }
+            pkP[n][0] = pack_bf16x2(pv[0], pv[1]);
+            pkP[n][1] = pack_bf16x2(pv[2], pv[3]);
+            pkD[n][0] = pack_bf16x2(dsv[0], dsv[1]);
+            pkD[n][1] = pack_bf16x2(dsv[2], dsv[3]);
           }
-          pkP[n][0] = pack_bf16x2(pv[0], pv[1]);
-          pkP[n][1] = pack_bf16x2(pv[2], pv[3]);
-          pkD[n][0] = pack_bf16x2(dsv[0], dsv[1]);
-          pkD[n][1] = pack_bf16x2(dsv[2], dsv[3]);
-        }
+        };
+        if (interior) softmax_tile(std::false_type{});
+        else softmax_tile(std::true_type{});
 
-        // dV += P^T dO ; dK += dS^T Q   (A via permlane, B from transposed LDS)
+        // dV += P^T dO ; dK += dS^T Q
         __builtin_amdgcn_s_setprio(1);
 #pragma unroll
         for (int ks2 = 0; ks2 < QBLK / 32; ++ks2) {
-          int avP[4], avD[4];
-          dfrag_to_at(pkP[2 * ks2], pkP[2 * ks2 + 1], avP);
-          dfrag_to_at(pkD[2 * ks2], pkD[2 * ks2 + 1], avD);
-          int4 aP4 = make_int4(avP[0], avP[1], avP[2], avP[3]);
-          int4 aD4 = make_int4(avD[0], avD[1], avD[2], avD[3]);
-          bf16x8 aP = *reinterpret_cast<bf16x8*>(&aP4);
-          bf16x8 aD = *reinterpret_cast<bf16x8*>(&aD4);
+          bf16x8 aP = own_a_frag(pkP[2 * ks2], pkP[2 * ks2 + 1]);
+          bf16x8 aD = own_a_frag(pkD[2 * ks2], pkD[2 * ks2 + 1]);
 #pragma unroll
           for (int n = 0; n < ND; ++n) {
-            int drow_ = n * 16 + c;
-            short8 t3 = *reinterpret_cast<const short8*>(&dOt_lds[drow_][swzb(drow_, ks2 * 4 + g) * 8]);
-            bf16x8 bdo = *reinterpret_cast<bf16x8*>(&t3);
-            short8 t4 = *reinterpret_cast<const short8*>(&Qt_lds[drow_][swzb(drow_, ks2 * 4 + g) * 8]);
-            bf16x8 bq = *reinterpret_cast<bf16x8*>(&t4);
+            bf16x8 bdo = read_b_tr<D>(&dO_lds[cur][0][0], trb, ks2 * 32, n);
+            bf16x8 bq = read_b_tr<D>(&Q_lds[cur][0][0], trb, ks2 * 32, n);
             dv_acc[n] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(aP, bdo, dv_acc[n], 0, 0, 0);
             dk_acc[n] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(aD, bq, dk_acc[n], 0, 0, 0);
           }
@@ -444,14 +557,14 @@ __global__ __launch_bounds__(512, 2) void attn_bwd_dkv_kernel(
       }
 
       if (have_next) {
-        __syncthreads();
+        // the other buffer was last read in iteration t-1, before that
+        // iteration's barrier
         __builtin_amdgcn_s_waitcnt(WAIT_VM0);
         __builtin_amdgcn_sched_barrier(0);
-        stage_writes(qt0 + QBLK);
-        __syncthreads();
+        stage_writes(cur ^ 1);
       }
+      __syncthreads();  // also the hg boundary: the next head restages buffer 0
     }
-    __syncthreads();  // hg boundary: next head restages from the prologue
   }
 
 #pragma unroll
@@ -469,636 +582,36 @@ __global__ __launch_bounds__(512, 2) void attn_bwd_dkv_kernel(
 }
 
 // ---------------------------------------------------------------------------
-// v4 dkv design (round-3 target; see profiles/README.md measurements):
-//   The v3 combined 32-row attempt spills (2 accumulator sets = 128 VGPRs
-//   minimum is fine, but the A/B operand sets on top are not).  Plan:
-//   phase 1 unchanged (8 waves x 16 kv rows compute S^T/dP^T per 64-q tile);
-//   then write packed bf16 P/dS tiles to LDS (64q x 128kv x 2 = 32 KB) and
-//   re-block PHASE 2 by (32-kv-row group, 64-d half): each wave keeps the
-//   same 64 accumulator VGPRs but every Qt/dOt B-read now feeds 2 MFMAs
-//   (two kv groups) and every P/dS A-read feeds 4 (ND=4 d-columns), cutting
-//   LDS bytes/MFMA from 16 to ~12 and deleting the permlane relayout chain.
-//   Cost: LDS rises 64->96 KB so occupancy drops 2->1 block/CU; whether the
-//   25% traffic cut beats the lost latency hiding must be MEASURED — if it
-//   loses, try folding Qt/dOt into the P/dS store instead (transpose during
-//   the phase-1->2 handoff) to stay at 2 blocks.
-// ---------------------------------------------------------------------------
-
-// ---------------------------------------------------------------------------
-// v3 kernels: 2x register blocking (32 output rows per wave, 256 per block).
-// Same technique stack as v2 plus the fwd-v2 lesson: every LDS A/B-operand
-// read now feeds 2 MFMAs instead of 1 (the kernels were LDS-read-bound, so
-// halving bytes-per-FLOP is the first-order lever).  S/dS tiles are
-// processed per 16-row q sub-tile immediately (backward has no online
-// softmax - lse/drow are known), keeping the transient register footprint
-// flat; packed P/dS live as 2x bf16 dwords until the phase-2 MFMAs.
-// ---------------------------------------------------------------------------
-
-// dq v3: 8 waves x 32 q rows (qt in {0,1}), kv tiles of 64.
-template <int D>
-__global__ __launch_bounds__(512) void attn_bwd_dq_kernel_v3(
-    const bf16* __restrict__ q, const bf16* __restrict__ k, const bf16* __restrict__ v,
-    const bf16* __restrict__ dout, const float* __restrict__ lse, const float* __restrict__ drow,
-    bf16* __restrict__ dq,
-    int sq, int skv, int b, int hq, int hkv, float scale, int causal, int window) {
-  constexpr int KVBLK = 64;
-  constexpr int ND = D / 16, NKD = D / 32;
-  constexpr int KCH = D / 8;
-  constexpr int SREG = KVBLK * D / 8 / 512;
-
-  __shared__ __align__(16) short K_lds[KVBLK][D];
-  __shared__ __align__(16) short V_lds[KVBLK][D];
-  __shared__ __align__(16) short Kt_lds[D][KVBLK];
-
-  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-  const int g = lane >> 4, c = lane & 15;
-  const int q0 = blockIdx.x * 256;
-  const int batch = blockIdx.y / hq, head = blockIdx.y % hq;
-  const int kv_head = head / (hq / hkv);
-  const long q_srow = (long)b * hq * D, k_srow = (long)b * hkv * D;
-  const bf16* qbase = q + ((long)batch * hq + head) * D;
-  const bf16* dobase = dout + ((long)batch * hq + head) * D;
-  const bf16* kbase = k + ((long)batch * hkv + kv_head) * D;
-  const bf16* vbase = v + ((long)batch * hkv + kv_head) * D;
-  bf16* dqbase = dq + ((long)batch * hq + head) * D;
-  const float* lse_row = lse + ((long)batch * hq + head) * sq;
-  const float* dr_row = drow + ((long)batch * hq + head) * sq;
-
-  const int row0 = q0 + wid * 32;
-  const int off = skv - sq;
-
-  bf16x8 qa[2][NKD], doa[2][NKD];
-  float my_lse_l2[2], my_dr_s[2];
-#pragma unroll
-  for (int qt = 0; qt < 2; ++qt) {
-    int qrow = min(row0 + qt * 16 + c, sq - 1);
-    const bf16* qr = qbase + (long)qrow * q_srow;
-    const bf16* dor = dobase + (long)qrow * q_srow;
-#pragma unroll
-    for (int kd = 0; kd < NKD; ++kd) {
-      short8 t1 = *reinterpret_cast<const short8*>(qr + kd * 32 + g * 8);
-      qa[qt][kd] = *reinterpret_cast<bf16x8*>(&t1);
-      short8 t2 = *reinterpret_cast<const short8*>(dor + kd * 32 + g * 8);
-      doa[qt][kd] = *reinterpret_cast<bf16x8*>(&t2);
-    }
-    my_lse_l2[qt] = lse_row[qrow] * LOG2E;
-    my_dr_s[qt] = dr_row[qrow] * scale;
-  }
-  const float c1 = scale * LOG2E;
-
-  f32x4 dq_acc[2][ND];
-#pragma unroll
-  for (int qt = 0; qt < 2; ++qt)
-#pragma unroll
-    for (int n = 0; n < ND; ++n) dq_acc[qt][n] = f32x4{0.f, 0.f, 0.f, 0.f};
-
-  int t_end = causal ? min((q0 + 255 + off) / KVBLK, (skv - 1) / KVBLK) : (skv - 1) / KVBLK;
-  int t_start = (window > 0) ? max(0, (q0 + off - window + 1) / KVBLK) : 0;
-
-  int st_row[SREG], st_c8[SREG], sv_row[SREG], sv_c8[SREG];
-#pragma unroll
-  for (int i = 0; i < SREG; ++i) {
-    int idx = (int)threadIdx.x + i * 512;
-    st_row[i] = idx / KCH;
-    st_c8[i] = idx % KCH;
-    sv_row[i] = idx & (KVBLK - 1);
-    sv_c8[i] = idx / KVBLK;
-  }
-
-  short8 kreg[SREG], vreg[SREG], ktreg[SREG];
-  auto stage_loads = [&](int k0) {
-#pragma unroll
-    for (int i = 0; i < SREG; ++i) {
-      int krow = k0 + st_row[i];
-      kreg[i] = short8{0, 0, 0, 0, 0, 0, 0, 0};
-      vreg[i] = short8{0, 0, 0, 0, 0, 0, 0, 0};
-      ktreg[i] = short8{0, 0, 0, 0, 0, 0, 0, 0};
-      if (krow < skv) {
-        kreg[i] = *reinterpret_cast<const short8*>(kbase + (long)krow * k_srow + st_c8[i] * 8);
-        vreg[i] = *reinterpret_cast<const short8*>(vbase + (long)krow * k_srow + st_c8[i] * 8);
-      }
-      int trow = k0 + sv_row[i];
-      if (trow < skv)
-        ktreg[i] = *reinterpret_cast<const short8*>(kbase + (long)trow * k_srow + sv_c8[i] * 8);
-    }
-  };
-  auto stage_writes = [&]() {
-#pragma unroll
-    for (int i = 0; i < SREG; ++i) {
-      *reinterpret_cast<short8*>(&K_lds[st_row[i]][swzb(st_row[i], st_c8[i]) * 8]) = kreg[i];
-      *reinterpret_cast<short8*>(&V_lds[st_row[i]][swzb(st_row[i], st_c8[i]) * 8]) = vreg[i];
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        int d = sv_c8[i] * 8 + j;
-        Kt_lds[d][swzb(d, sv_row[i] >> 3) * 8 + (sv_row[i] & 7)] = ktreg[i][j];
-      }
-    }
-  };
-
-  stage_loads(t_start * KVBLK);
-  stage_writes();
-  __syncthreads();
-
-  for (int t = t_start; t <= t_end; ++t) {
-    const int k0 = t * KVBLK;
-    const bool have_next = (t + 1 <= t_end);
-    if (have_next) stage_loads(k0 + KVBLK);
-
-    bool wave_skip = (causal && k0 > row0 + 31 + off) ||
-                     (window > 0 && k0 + KVBLK - 1 < row0 + off - window + 1);
-    if (!wave_skip) {
-      // per 16-row kv sub-tile: S^T/dP^T MFMAs -> dS -> packed pairs
-      int pk[KVBLK / 16][2][2];  // [n][qt][pair]
-      __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-      for (int n = 0; n < KVBLK / 16; ++n) {
-        f32x4 st[2], dpt[2];
-#pragma unroll
-        for (int qt = 0; qt < 2; ++qt) {
-          st[qt] = f32x4{0.f, 0.f, 0.f, 0.f};
-          dpt[qt] = f32x4{0.f, 0.f, 0.f, 0.f};
-        }
-        int krow = n * 16 + c;
-#pragma unroll
-        for (int kd = 0; kd < NKD; ++kd) {
-          short8 t1 = *reinterpret_cast<const short8*>(&K_lds[krow][swzb(krow, kd * 4 + g) * 8]);
-          bf16x8 ak = *reinterpret_cast<bf16x8*>(&t1);
-          short8 t2 = *reinterpret_cast<const short8*>(&V_lds[krow][swzb(krow, kd * 4 + g) * 8]);
-          bf16x8 av = *reinterpret_cast<bf16x8*>(&t2);
-#pragma unroll
-          for (int qt = 0; qt < 2; ++qt) {
-            st[qt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ak, qa[qt][kd], st[qt], 0, 0, 0);
-            dpt[qt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(av, doa[qt][kd], dpt[qt], 0, 0, 0);
-          }
-        }
-#pragma unroll
-        for (int qt = 0; qt < 2; ++qt) {
-          const int qrow = row0 + qt * 16 + c;
-          float ds[4];
-#pragma unroll
-          for (int r = 0; r < 4; ++r) {
-            int kvrow = k0 + n * 16 + g * 4 + r;
-            bool ok = (kvrow < skv) && (qrow < sq);
-            if (causal) ok &= (kvrow <= qrow + off);
-            if (window > 0) ok &= (kvrow > qrow + off - window);
-            float pt = ok ? exp2f(__builtin_fmaf(st[qt][r], c1, -my_lse_l2[qt])) : 0.f;
-            ds[r] = pt * __builtin_fmaf(dpt[qt][r], scale, -my_dr_s[qt]);
-          }
-          pk[n][qt][0] = pack_bf16x2(ds[0], ds[1]);
-          pk[n][qt][1] = pack_bf16x2(ds[2], ds[3]);
-        }
-      }
-
-      // dq += dS K : one Kt load feeds both qt MFMAs
-#pragma unroll
-      for (int ks2 = 0; ks2 < KVBLK / 32; ++ks2) {
-        bf16x8 a[2];
-#pragma unroll
-        for (int qt = 0; qt < 2; ++qt) {
-          int av4[4];
-          dfrag_to_at(pk[2 * ks2][qt], pk[2 * ks2 + 1][qt], av4);
-          int4 av = make_int4(av4[0], av4[1], av4[2], av4[3]);
-          a[qt] = *reinterpret_cast<bf16x8*>(&av);
-        }
-#pragma unroll
-        for (int n = 0; n < ND; ++n) {
-          int vrow = n * 16 + c;
-          short8 t3 = *reinterpret_cast<const short8*>(&Kt_lds[vrow][swzb(vrow, ks2 * 4 + g) * 8]);
-          bf16x8 bK = *reinterpret_cast<bf16x8*>(&t3);
-#pragma unroll
-          for (int qt = 0; qt < 2; ++qt)
-            dq_acc[qt][n] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[qt], bK, dq_acc[qt][n], 0, 0, 0);
-        }
-      }
-      __builtin_amdgcn_s_setprio(0);
-    }
-
-    if (have_next) {
-      __syncthreads();
-      __builtin_amdgcn_s_waitcnt(WAIT_VM0);
-      __builtin_amdgcn_sched_barrier(0);
-      stage_writes();
-      __syncthreads();
-    }
-  }
-
-#pragma unroll
-  for (int qt = 0; qt < 2; ++qt)
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      int row = row0 + qt * 16 + g * 4 + r;
-      if (row >= sq) continue;
-      bf16* dqr = dqbase + (long)row * q_srow;
-#pragma unroll
-      for (int n = 0; n < ND; ++n) dqr[n * 16 + c] = f2bf(dq_acc[qt][n][r]);
-    }
-}
-
-// dv v3: 8 waves x 32 kv rows (kvt in {0,1}), q tiles of 64, GQA heads looped.
-// dv = P^T dO only (dk split into its own kernel: the combined 32-row
-// version needs 2x f32 accumulators and spills 261 VGPRs; the split costs a
-// recomputed S GEMM but keeps both kernels at 2 waves/SIMD with 0 spills).
-template <int D>
-__global__ __launch_bounds__(512) void attn_bwd_dv_kernel_v3(
-    const bf16* __restrict__ q, const bf16* __restrict__ k, const bf16* __restrict__ v,
-    const bf16* __restrict__ dout, const float* __restrict__ lse, const float* __restrict__ drow,
-    bf16* __restrict__ dv,
-    int sq, int skv, int b, int hq, int hkv, float scale, int causal, int window) {
-  constexpr int QBLK = 64;
-  constexpr int ND = D / 16, NKD = D / 32;
-  constexpr int KCH = D / 8;
-  constexpr int SREG = QBLK * D / 8 / 512;
-
-  __shared__ __align__(16) short Q_lds[QBLK][D];
-  __shared__ __align__(16) short dOt_lds[D][QBLK];
-  __shared__ float lse_s[QBLK];
-
-  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-  const int g = lane >> 4, c = lane & 15;
-  const int k0 = blockIdx.x * 256;
-  const int batch = blockIdx.y / hkv, kv_head = blockIdx.y % hkv;
-  const int rep = hq / hkv;
-  const long q_srow = (long)b * hq * D, k_srow = (long)b * hkv * D;
-  const bf16* kbase = k + ((long)batch * hkv + kv_head) * D;
-  bf16* dvbase = dv + ((long)batch * hkv + kv_head) * D;
-
-  const int krow0 = k0 + wid * 32;
-  const int off = skv - sq;
-  const float c1 = scale * LOG2E;
-
-  bf16x8 ka[2][NKD];
-#pragma unroll
-  for (int kvt = 0; kvt < 2; ++kvt) {
-    int krow = min(krow0 + kvt * 16 + c, skv - 1);
-    const bf16* kr = kbase + (long)krow * k_srow;
-#pragma unroll
-    for (int kd = 0; kd < NKD; ++kd) {
-      short8 t1 = *reinterpret_cast<const short8*>(kr + kd * 32 + g * 8);
-      ka[kvt][kd] = *reinterpret_cast<bf16x8*>(&t1);
-    }
-  }
-
-  f32x4 dv_acc[2][ND];
-#pragma unroll
-  for (int kvt = 0; kvt < 2; ++kvt)
-#pragma unroll
-    for (int n = 0; n < ND; ++n) dv_acc[kvt][n] = f32x4{0.f, 0.f, 0.f, 0.f};
-
-  int tq_start = causal ? max(0, (k0 - off) / QBLK) : 0;
-  int tq_end = (sq - 1) / QBLK;
-  if (window > 0) tq_end = min(tq_end, (k0 + 255 - off + window - 1) / QBLK);
-
-  int st_row[SREG], st_c8[SREG], sv_row[SREG], sv_c8[SREG];
-#pragma unroll
-  for (int i = 0; i < SREG; ++i) {
-    int idx = (int)threadIdx.x + i * 512;
-    st_row[i] = idx / KCH;
-    st_c8[i] = idx % KCH;
-    sv_row[i] = idx & (QBLK - 1);
-    sv_c8[i] = idx / QBLK;
-  }
-
-  for (int hg = 0; hg < rep; ++hg) {
-    const int head = kv_head * rep + hg;
-    const bf16* qbase = q + ((long)batch * hq + head) * D;
-    const bf16* dobase = dout + ((long)batch * hq + head) * D;
-    const float* lse_row = lse + ((long)batch * hq + head) * sq;
-
-    short8 qrm[SREG], dotr[SREG];
-    auto stage_loads = [&](int qt0) {
-#pragma unroll
-      for (int i = 0; i < SREG; ++i) {
-        int r1 = qt0 + st_row[i];
-        qrm[i] = short8{0, 0, 0, 0, 0, 0, 0, 0};
-        dotr[i] = short8{0, 0, 0, 0, 0, 0, 0, 0};
-        if (r1 < sq)
-          qrm[i] = *reinterpret_cast<const short8*>(qbase + (long)r1 * q_srow + st_c8[i] * 8);
-        int r2 = qt0 + sv_row[i];
-        if (r2 < sq)
-          dotr[i] = *reinterpret_cast<const short8*>(dobase + (long)r2 * q_srow + sv_c8[i] * 8);
-      }
-    };
-    auto stage_writes = [&](int qt0) {
-#pragma unroll
-      for (int i = 0; i < SREG; ++i) {
-        *reinterpret_cast<short8*>(&Q_lds[st_row[i]][swzb(st_row[i], st_c8[i]) * 8]) = qrm[i];
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-          int d = sv_c8[i] * 8 + j;
-          dOt_lds[d][swzb(d, sv_row[i] >> 3) * 8 + (sv_row[i] & 7)] = dotr[i][j];
-        }
-      }
-      if (threadIdx.x < QBLK) {
-        int qi = min(qt0 + (int)threadIdx.x, sq - 1);
-        lse_s[threadIdx.x] = lse_row[qi] * LOG2E;
-      }
-    };
-
-    stage_loads(tq_start * QBLK);
-    stage_writes(tq_start * QBLK);
-    __syncthreads();
-
-    for (int t = tq_start; t <= tq_end; ++t) {
-      const int qt0 = t * QBLK;
-      const bool have_next = (t + 1 <= tq_end);
-      if (have_next) stage_loads(qt0 + QBLK);
-
-      bool wave_skip = (causal && qt0 + QBLK - 1 < krow0 - off) ||
-                       (window > 0 && qt0 >= krow0 + 31 - off + window);
-      if (!wave_skip) {
-        int pkP[QBLK / 16][2][2];  // [n][kvt][pair]
-        __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-        for (int n = 0; n < QBLK / 16; ++n) {
-          f32x4 st[2];
-          st[0] = f32x4{0.f, 0.f, 0.f, 0.f};
-          st[1] = f32x4{0.f, 0.f, 0.f, 0.f};
-          int qrow = n * 16 + c;
-#pragma unroll
-          for (int kd = 0; kd < NKD; ++kd) {
-            short8 t1 = *reinterpret_cast<const short8*>(&Q_lds[qrow][swzb(qrow, kd * 4 + g) * 8]);
-            bf16x8 aq = *reinterpret_cast<bf16x8*>(&t1);
-#pragma unroll
-            for (int kvt = 0; kvt < 2; ++kvt)
-              st[kvt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(aq, ka[kvt][kd], st[kvt], 0, 0, 0);
-          }
-#pragma unroll
-          for (int kvt = 0; kvt < 2; ++kvt) {
-            const int kvcol = krow0 + kvt * 16 + c;
-            float pv[4];
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-              int qi = n * 16 + g * 4 + r;
-              int qrow_ = qt0 + qi;
-              bool ok = (kvcol < skv) && (qrow_ < sq);
-              if (causal) ok &= (kvcol <= qrow_ + off);
-              if (window > 0) ok &= (kvcol > qrow_ + off - window);
-              pv[r] = ok ? exp2f(__builtin_fmaf(st[kvt][r], c1, -lse_s[qi])) : 0.f;
-            }
-            pkP[n][kvt][0] = pack_bf16x2(pv[0], pv[1]);
-            pkP[n][kvt][1] = pack_bf16x2(pv[2], pv[3]);
-          }
-        }
-
-        // dV += P^T dO : one dOt load feeds both kvt MFMAs
-#pragma unroll
-        for (int ks2 = 0; ks2 < QBLK / 32; ++ks2) {
-          bf16x8 aP[2];
-#pragma unroll
-          for (int kvt = 0; kvt < 2; ++kvt) {
-            int avP[4];
-            dfrag_to_at(pkP[2 * ks2][kvt], pkP[2 * ks2 + 1][kvt], avP);
-            int4 aP4 = make_int4(avP[0], avP[1], avP[2], avP[3]);
-            aP[kvt] = *reinterpret_cast<bf16x8*>(&aP4);
-          }
-#pragma unroll
-          for (int n = 0; n < ND; ++n) {
-            int drow_ = n * 16 + c;
-            short8 t3 = *reinterpret_cast<const short8*>(&dOt_lds[drow_][swzb(drow_, ks2 * 4 + g) * 8]);
-            bf16x8 bdo = *reinterpret_cast<bf16x8*>(&t3);
-#pragma unroll
-            for (int kvt = 0; kvt < 2; ++kvt)
-              dv_acc[kvt][n] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(aP[kvt], bdo, dv_acc[kvt][n], 0, 0, 0);
-          }
-        }
-        __builtin_amdgcn_s_setprio(0);
-      }
-
-      if (have_next) {
-        __syncthreads();
-        __builtin_amdgcn_s_waitcnt(WAIT_VM0);
-        __builtin_amdgcn_sched_barrier(0);
-        stage_writes(qt0 + QBLK);
-        __syncthreads();
-      }
-    }
-    __syncthreads();
-  }
-
-#pragma unroll
-  for (int kvt = 0; kvt < 2; ++kvt)
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      int row = krow0 + kvt * 16 + g * 4 + r;
-      if (row >= skv) continue;
-      bf16* dvr = dvbase + (long)row * k_srow;
-#pragma unroll
-      for (int n = 0; n < ND; ++n) dvr[n * 16 + c] = f2bf(dv_acc[kvt][n][r]);
-    }
-}
-
-// dk v3: 8 waves x 32 kv rows, dk = dS^T Q with dS = P*(scale*dP - drow).
-// A-fragments (Q, dO rows) are read DIRECTLY FROM GLOBAL in the S/dP phase:
-// all 8 waves read the same 32 KB tile, so after the first touch the reads
-// are L1/L2 hits, and dropping the Q_lds/dO_lds tiles + their staging
-// registers is what keeps this kernel at 2 waves/SIMD without spills (the
-// LDS-staged variant spilled 126 VGPRs).  Only the transposed Qt tile (the
-// phase-2 B operand) stays in LDS.
-template <int D>
-__global__ __launch_bounds__(512) void attn_bwd_dk_kernel_v3(
-    const bf16* __restrict__ q, const bf16* __restrict__ k, const bf16* __restrict__ v,
-    const bf16* __restrict__ dout, const float* __restrict__ lse, const float* __restrict__ drow,
-    bf16* __restrict__ dk,
-    int sq, int skv, int b, int hq, int hkv, float scale, int causal, int window) {
-  constexpr int QBLK = 64;
-  constexpr int ND = D / 16, NKD = D / 32;
-  constexpr int SREG = QBLK * D / 8 / 512;
-
-  __shared__ __align__(16) short Qt_lds[D][QBLK];
-  __shared__ float lse_s[QBLK];
-  __shared__ float dr_s[QBLK];
-
-  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-  const int g = lane >> 4, c = lane & 15;
-  const int k0 = blockIdx.x * 256;
-  const int batch = blockIdx.y / hkv, kv_head = blockIdx.y % hkv;
-  const int rep = hq / hkv;
-  const long q_srow = (long)b * hq * D, k_srow = (long)b * hkv * D;
-  const bf16* kbase = k + ((long)batch * hkv + kv_head) * D;
-  const bf16* vbase = v + ((long)batch * hkv + kv_head) * D;
-  bf16* dkbase = dk + ((long)batch * hkv + kv_head) * D;
-
-  const int krow0 = k0 + wid * 32;
-  const int off = skv - sq;
-  const float c1 = scale * LOG2E;
-
-  bf16x8 ka[2][NKD], va[2][NKD];
-#pragma unroll
-  for (int kvt = 0; kvt < 2; ++kvt) {
-    int krow = min(krow0 + kvt * 16 + c, skv - 1);
-    const bf16* kr = kbase + (long)krow * k_srow;
-    const bf16* vr = vbase + (long)krow * k_srow;
-#pragma unroll
-    for (int kd = 0; kd < NKD; ++kd) {
-      short8 t1 = *reinterpret_cast<const short8*>(kr + kd * 32 + g * 8);
-      ka[kvt][kd] = *reinterpret_cast<bf16x8*>(&t1);
-      short8 t2 = *reinterpret_cast<const short8*>(vr + kd * 32 + g * 8);
-      va[kvt][kd] = *reinterpret_cast<bf16x8*>(&t2);
-    }
-  }
-
-  f32x4 dk_acc[2][ND];
-#pragma unroll
-  for (int kvt = 0; kvt < 2; ++kvt)
-#pragma unroll
-    for (int n = 0; n < ND; ++n) dk_acc[kvt][n] = f32x4{0.f, 0.f, 0.f, 0.f};
-
-  int tq_start = causal ? max(0, (k0 - off) / QBLK) : 0;
-  int tq_end = (sq - 1) / QBLK;
-  if (window > 0) tq_end = min(tq_end, (k0 + 255 - off + window - 1) / QBLK);
-
-  int sv_row[SREG], sv_c8[SREG];
-#pragma unroll
-  for (int i = 0; i < SREG; ++i) {
-    int idx = (int)threadIdx.x + i * 512;
-    sv_row[i] = idx & (QBLK - 1);
-    sv_c8[i] = idx / QBLK;
-  }
-
-  for (int hg = 0; hg < rep; ++hg) {
-    const int head = kv_head * rep + hg;
-    const bf16* qbase = q + ((long)batch * hq + head) * D;
-    const bf16* dobase = dout + ((long)batch * hq + head) * D;
-    const float* lse_row = lse + ((long)batch * hq + head) * sq;
-    const float* dr_row = drow + ((long)batch * hq + head) * sq;
-
-    short8 qtr[SREG];
-    auto stage_loads = [&](int qt0) {
-#pragma unroll
-      for (int i = 0; i < SREG; ++i) {
-        qtr[i] = short8{0, 0, 0, 0, 0, 0, 0, 0};
-        int r2 = qt0 + sv_row[i];
-        if (r2 < sq)
-          qtr[i] = *reinterpret_cast<const short8*>(qbase + (long)r2 * q_srow + sv_c8[i] * 8);
-      }
-    };
-    auto stage_writes = [&](int qt0) {
-#pragma unroll
-      for (int i = 0; i < SREG; ++i) {
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-          int d = sv_c8[i] * 8 + j;
-          Qt_lds[d][swzb(d, sv_row[i] >> 3) * 8 + (sv_row[i] & 7)] = qtr[i][j];
-        }
-      }
-      if (threadIdx.x < QBLK) {
-        int qi = min(qt0 + (int)threadIdx.x, sq - 1);
-        lse_s[threadIdx.x] = lse_row[qi] * LOG2E;
-        dr_s[threadIdx.x] = dr_row[qi] * scale;
-      }
-    };
-
-    stage_loads(tq_start * QBLK);
-    stage_writes(tq_start * QBLK);
-    __syncthreads();
-
-    for (int t = tq_start; t <= tq_end; ++t) {
-      const int qt0 = t * QBLK;
-      const bool have_next = (t + 1 <= tq_end);
-      if (have_next) stage_loads(qt0 + QBLK);
-
-      bool wave_skip = (causal && qt0 + QBLK - 1 < krow0 - off) ||
-                       (window > 0 && qt0 >= krow0 + 31 - off + window);
-      if (!wave_skip) {
-        // per n-pair: S/dP MFMAs -> dS packs for n and n+1, then immediately
-        // the ks2 = n/2 slice of dK += dS^T Q (keeps only 2 pkD slots live)
-        int pkD[2][2][2];  // [n&1][kvt][pair]
-        __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-        for (int n = 0; n < QBLK / 16; ++n) {
-          f32x4 st[2], dpt[2];
-#pragma unroll
-          for (int kvt = 0; kvt < 2; ++kvt) {
-            st[kvt] = f32x4{0.f, 0.f, 0.f, 0.f};
-            dpt[kvt] = f32x4{0.f, 0.f, 0.f, 0.f};
-          }
-          int qrow = min(qt0 + n * 16 + c, sq - 1);
-          const bf16* qr = qbase + (long)qrow * q_srow;
-          const bf16* dor = dobase + (long)qrow * q_srow;
-#pragma unroll
-          for (int kd = 0; kd < NKD; ++kd) {
-            short8 t1 = *reinterpret_cast<const short8*>(qr + kd * 32 + g * 8);
-            bf16x8 aq = *reinterpret_cast<bf16x8*>(&t1);
-            short8 t2 = *reinterpret_cast<const short8*>(dor + kd * 32 + g * 8);
-            bf16x8 ado = *reinterpret_cast<bf16x8*>(&t2);
-#pragma unroll
-            for (int kvt = 0; kvt < 2; ++kvt) {
-              st[kvt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(aq, ka[kvt][kd], st[kvt], 0, 0, 0);
-              dpt[kvt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ado, va[kvt][kd], dpt[kvt], 0, 0, 0);
-            }
-          }
-#pragma unroll
-          for (int kvt = 0; kvt < 2; ++kvt) {
-            const int kvcol = krow0 + kvt * 16 + c;
-            float dsv[4];
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-              int qi = n * 16 + g * 4 + r;
-              int qrow_ = qt0 + qi;
-              bool ok = (kvcol < skv) && (qrow_ < sq);
-              if (causal) ok &= (kvcol <= qrow_ + off);
-              if (window > 0) ok &= (kvcol > qrow_ + off - window);
-              float pt = ok ? exp2f(__builtin_fmaf(st[kvt][r], c1, -lse_s[qi])) : 0.f;
-              dsv[r] = pt * __builtin_fmaf(dpt[kvt][r], scale, -dr_s[qi]);
-            }
-            pkD[n & 1][kvt][0] = pack_bf16x2(dsv[0], dsv[1]);
-            pkD[n & 1][kvt][1] = pack_bf16x2(dsv[2], dsv[3]);
-          }
-          if (n & 1) {
-            const int ks2 = n >> 1;
-            bf16x8 aD[2];
-#pragma unroll
-            for (int kvt = 0; kvt < 2; ++kvt) {
-              int avD[4];
-              dfrag_to_at(pkD[0][kvt], pkD[1][kvt], avD);
-              int4 aD4 = make_int4(avD[0], avD[1], avD[2], avD[3]);
-              aD[kvt] = *reinterpret_cast<bf16x8*>(&aD4);
-            }
-#pragma unroll
-            for (int nd = 0; nd < ND; ++nd) {
-              int drow_ = nd * 16 + c;
-              short8 t4 = *reinterpret_cast<const short8*>(&Qt_lds[drow_][swzb(drow_, ks2 * 4 + g) * 8]);
-              bf16x8 bq = *reinterpret_cast<bf16x8*>(&t4);
-#pragma unroll
-              for (int kvt = 0; kvt < 2; ++kvt)
-                dk_acc[kvt][nd] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(aD[kvt], bq, dk_acc[kvt][nd], 0, 0, 0);
-            }
-          }
-        }
-        __builtin_amdgcn_s_setprio(0);
-      }
-
-      if (have_next) {
-        __syncthreads();
-        __builtin_amdgcn_s_waitcnt(WAIT_VM0);
-        __builtin_amdgcn_sched_barrier(0);
-        stage_writes(qt0 + QBLK);
-        __syncthreads();
-      }
-    }
-    __syncthreads();
-  }
-
-#pragma unroll
-  for (int kvt = 0; kvt < 2; ++kvt)
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      int row = krow0 + kvt * 16 + g * 4 + r;
-      if (row >= skv) continue;
-      bf16* dkr = dkbase + (long)row * k_srow;
-#pragma unroll
-      for (int n = 0; n < ND; ++n) dkr[n * 16 + c] = f2bf(dk_acc[kvt][n][r]);
-    }
-}
-
-// ---------------------------------------------------------------------------
 // host wrapper
 // ---------------------------------------------------------------------------
+template <int D, int QT>
+static void launch_dq(dim3 grid, hipStream_t stream, const torch::Tensor& q, const torch::Tensor& k,
+                      const torch::Tensor& v, const torch::Tensor& dout, const torch::Tensor& lse,
+                      const torch::Tensor& drow, torch::Tensor& dq, int sq, int skv, int b, int hq, int hkv,
+                      float scale, int causal, int window) {
+  hipLaunchKernelGGL((attn_bwd_dq_kernel<D, QT>), grid, dim3(512), 0, stream,
+                     (const bf16*)q.data_ptr(), (const bf16*)k.data_ptr(), (const bf16*)v.data_ptr(),
+                     (const bf16*)dout.data_ptr(), lse.data_ptr<float>(), drow.data_ptr<float>(),
+                     (bf16*)dq.data_ptr(), sq, skv, b, hq, hkv, scale, causal, window);
+}
+
+template <int D>
+static void launch_dkv(dim3 grid, hipStream_t stream, const torch::Tensor& q, const torch::Tensor& k,
+                       const torch::Tensor& v, const torch::Tensor& dout, const torch::Tensor& lse,
+                       const torch::Tensor& drow, torch::Tensor& dk, torch::Tensor& dv, int sq, int skv, int b,
+                       int hq, int hkv, float scale, int causal, int window) {
+  hipLaunchKernelGGL((attn_bwd_dkv_kernel<D>), grid, dim3(512), 0, stream,
+                     (const bf16*)q.data_ptr(), (const bf16*)k.data_ptr(), (const bf16*)v.data_ptr(),
+                     (const bf16*)dout.data_ptr(), lse.data_ptr<float>(), drow.data_ptr<float>(),
+                     (bf16*)dk.data_ptr(), (bf16*)dv.data_ptr(), sq, skv, b, hq, hkv, scale, causal, window);
+}
+
 std::vector<torch::Tensor> attn_bwd(torch::Tensor dout, torch::Tensor q, torch::Tensor k,
                                     torch::Tensor v, torch::Tensor out, torch::Tensor lse,
                                     bool causal, double scale, long window) {
   int sq = q.size(0), b = q.size(1), hq = q.size(2), d = q.size(3);
   int skv = k.size(0), hkv = k.size(2);
+  TORCH_CHECK(d == 64 || d == 128, "attn_bwd: head dim must be 64 or 128");
   auto qc = q.contiguous(), kc = k.contiguous(), vc = v.contiguous();
   auto doc = dout.contiguous(), oc = out.contiguous();
   auto dq = torch::empty_like(qc);
@@ -1113,55 +626,23 @@ std::vector<torch::Tensor> attn_bwd(torch::Tensor dout, torch::Tensor q, torch::
                      (const short8*)doc.data_ptr(), (const short8*)oc.data_ptr(),
                      drow.data_ptr<float>(), rows, b * hq, sq, d8);
 
-  // v3 (32 rows/wave register blocking) for long sequences; v2 fallback via
-  // env or when the sequence is too short to fill 256-row blocks.
-  static const bool force_v2 = getenv("MEGATRON_AMD_ATTN_BWD_V2") != nullptr;
-  const bool use_v3_dq = !force_v2 && sq >= 256;
-  // dv/dk split (v3) measured slower than the combined v2 dkv at s=4096
-  // (dk's global A-fragment reads thrash L1; see profiles/README.md round-2
-  // notes) - combined v2 stays the default, split kept for future work.
-  static const bool force_dkv_v3 = getenv("MEGATRON_AMD_ATTN_DKV_V3") != nullptr;
-  const bool use_v3_dkv = force_dkv_v3 && !force_v2 && skv >= 256;
-  dim3 grid_dq((sq + (use_v3_dq ? 255 : 127)) / (use_v3_dq ? 256 : 128), b * hq);
-  dim3 grid_dkv((skv + (use_v3_dkv ? 255 : 127)) / (use_v3_dkv ? 256 : 128), b * hkv);
+  // 256-row dq blocks (32 q rows per wave) for long sequences; 128-row blocks
+  // via env, for D = 64, or when the sequence is too short to fill 256 rows.
+  static const bool force_128 = getenv("MEGATRON_AMD_ATTN_BWD_V2") != nullptr;
+  const bool dq_256 = !force_128 && sq >= 256 && d == 128;
+  dim3 grid_dq((sq + (dq_256 ? 255 : 127)) / (dq_256 ? 256 : 128), b * hq);
+  dim3 grid_dkv((skv + 127) / 128, b * hkv);
+  const float fs = (float)scale;
+  const int ic = causal ? 1 : 0, iw = (int)window;
   if (d == 128) {
-    if (use_v3_dq)
-      hipLaunchKernelGGL((attn_bwd_dq_kernel_v3<128>), grid_dq, dim3(512), 0, stream,
-                         (const bf16*)qc.data_ptr(), (const bf16*)kc.data_ptr(), (const bf16*)vc.data_ptr(),
-                         (const bf16*)doc.data_ptr(), lse.data_ptr<float>(), drow.data_ptr<float>(),
-                         (bf16*)dq.data_ptr(), sq, skv, b, hq, hkv, (float)scale, causal ? 1 : 0, (int)window);
+    if (dq_256)
+      launch_dq<128, 2>(grid_dq, stream, qc, kc, vc, doc, lse, drow, dq, sq, skv, b, hq, hkv, fs, ic, iw);
     else
-      hipLaunchKernelGGL((attn_bwd_dq_kernel<128>), grid_dq, dim3(512), 0, stream,
-                         (const bf16*)qc.data_ptr(), (const bf16*)kc.data_ptr(), (const bf16*)vc.data_ptr(),
-                         (const bf16*)doc.data_ptr(), lse.data_ptr<float>(), drow.data_ptr<float>(),
-                         (bf16*)dq.data_ptr(), sq, skv, b, hq, hkv, (float)scale, causal ? 1 : 0, (int)window);
-    if (use_v3_dkv) {
-      hipLaunchKernelGGL((attn_bwd_dv_kernel_v3<128>), grid_dkv, dim3(512), 0, stream,
-                         (const bf16*)qc.data_ptr(), (const bf16*)kc.data_ptr(), (const bf16*)vc.data_ptr(),
-                         (const bf16*)doc.data_ptr(), lse.data_ptr<float>(), drow.data_ptr<float>(),
-                         (bf16*)dv.data_ptr(),
-                         sq, skv, b, hq, hkv, (float)scale, causal ? 1 : 0, (int)window);
-      hipLaunchKernelGGL((attn_bwd_dk_kernel_v3<128>), grid_dkv, dim3(512), 0, stream,
-                         (const bf16*)qc.data_ptr(), (const bf16*)kc.data_ptr(), (const bf16*)vc.data_ptr(),
-                         (const bf16*)doc.data_ptr(), lse.data_ptr<float>(), drow.data_ptr<float>(),
-                         (bf16*)dk.data_ptr(),
-                         sq, skv, b, hq, hkv, (float)scale, causal ? 1 : 0, (int)window);
-    } else
-      hipLaunchKernelGGL((attn_bwd_dkv_kernel<128>), grid_dkv, dim3(512), 0, stream,
-                         (const bf16*)qc.data_ptr(), (const bf16*)kc.data_ptr(), (const bf16*)vc.data_ptr(),
-                         (const bf16*)doc.data_ptr(), lse.data_ptr<float>(), drow.data_ptr<float>(),
-                         (bf16*)dk.data_ptr(), (bf16*)dv.data_ptr(),
-                         sq, skv, b, hq, hkv, (float)scale, causal ? 1 : 0, (int)window);
+      launch_dq<128, 1>(grid_dq, stream, qc, kc, vc, doc, lse, drow, dq, sq, skv, b, hq, hkv, fs, ic, iw);
+    launch_dkv<128>(grid_dkv, stream, qc, kc, vc, doc, lse, drow, dk, dv, sq, skv, b, hq, hkv, fs, ic, iw);
   } else {
-    hipLaunchKernelGGL((attn_bwd_dq_kernel<64>), grid_dq, dim3(512), 0, stream,
-                       (const bf16*)qc.data_ptr(), (const bf16*)kc.data_ptr(), (const bf16*)vc.data_ptr(),
-                       (const bf16*)doc.data_ptr(), lse.data_ptr<float>(), drow.data_ptr<float>(),
-                       (bf16*)dq.data_ptr(), sq, skv, b, hq, hkv, (float)scale, causal ? 1 : 0, (int)window);
-    hipLaunchKernelGGL((attn_bwd_dkv_kernel<64>), grid_dkv, dim3(512), 0, stream,
-                       (const bf16*)qc.data_ptr(), (const bf16*)kc.data_ptr(), (const bf16*)vc.data_ptr(),
-                       (const bf16*)doc.data_ptr(), lse.data_ptr<float>(), drow.data_ptr<float>(),
-                       (bf16*)dk.data_ptr(), (bf16*)dv.data_ptr(),
-                       sq, skv, b, hq, hkv, (float)scale, causal ? 1 : 0, (int)window);
+    launch_dq<64, 1>(grid_dq, stream, qc, kc, vc, doc, lse, drow, dq, sq, skv, b, hq, hkv, fs, ic, iw);
+    launch_dkv<64>(grid_dkv, stream, qc, kc, vc, doc, lse, drow, dk, dv, sq, skv, b, hq, hkv, fs, ic, iw);
   }
   return {dq, dk, dv};
 }
