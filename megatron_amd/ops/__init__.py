@@ -199,6 +199,36 @@ def flash_attention(q, k, v, causal=True, scale=None, window=None):
     return ref.attention(q, k, v, causal=causal, scale=scale, window=window)
 
 
+class _FlashAttnVarlenFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, q, k, v, cu_seqlens, causal, scale):
+        out, lse = _C.attn_varlen_fwd(q, k, v, cu_seqlens, causal, scale)
+        ctx.save_for_backward(q, k, v, out, lse, cu_seqlens)
+        ctx.causal, ctx.scale = causal, scale
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        q, k, v, out, lse, cu_seqlens = ctx.saved_tensors
+        dq, dk, dv = _C.attn_varlen_bwd(dout.contiguous(), q, k, v, out, lse, cu_seqlens, ctx.causal, ctx.scale)
+        return dq, dk, dv, None, None, None
+
+
+def flash_attention_varlen(q, k, v, cu_seqlens, causal=True, scale=None):
+    """Packed (THD) attention: q [t, 1, hq, d], k/v [t, 1, hkv, d], documents
+    at cu_seqlens [n_docs + 1]; each token attends inside its own document.
+    cu_seqlens stays on the device (no host read, graph-capturable)."""
+    d = q.shape[-1]
+    if scale is None:
+        scale = 1.0 / math.sqrt(d)
+    # the MFMA kernels tile for bf16, d in {64, 128} and one head dim for q/k/v
+    # (MLA with dqk != dv, test-size heads and fp32 take the plain-PyTorch path)
+    if _use_native(q) and q.dtype == torch.bfloat16 and d in (64, 128) and v.shape[-1] == d:
+        cu = cu_seqlens.to(device=q.device, dtype=torch.int32).contiguous()
+        return _FlashAttnVarlenFn.apply(q.contiguous(), k.contiguous(), v.contiguous(), cu, causal, scale)
+    return ref.attention_varlen(q, k, v, cu_seqlens.to(q.device), causal=causal, scale=scale)
+
+
 # ---------------------------------------------------------------------------
 # wgrad GEMM with fp32 accumulation  (K9)
 # ---------------------------------------------------------------------------

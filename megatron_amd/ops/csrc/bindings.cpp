@@ -18,6 +18,11 @@ std::vector<torch::Tensor> attn_fwd(torch::Tensor q, torch::Tensor k, torch::Ten
 std::vector<torch::Tensor> attn_bwd(torch::Tensor dout, torch::Tensor q, torch::Tensor k,
                                     torch::Tensor v, torch::Tensor out, torch::Tensor lse,
                                     bool causal, double scale, long window);
+std::vector<torch::Tensor> attn_varlen_fwd(torch::Tensor q, torch::Tensor k, torch::Tensor v,
+                                           torch::Tensor cu_seqlens, bool causal, double scale);
+std::vector<torch::Tensor> attn_varlen_bwd(torch::Tensor dout, torch::Tensor q, torch::Tensor k,
+                                           torch::Tensor v, torch::Tensor out, torch::Tensor lse,
+                                           torch::Tensor cu_seqlens, bool causal, double scale);
 std::vector<torch::Tensor> ce_fwd(torch::Tensor logits, torch::Tensor target, long vocab_start);
 void ce_bwd(torch::Tensor logits, torch::Tensor target, torch::Tensor row_max,
             torch::Tensor row_inv_sumexp, torch::Tensor grad_out, long vocab_start);
@@ -46,6 +51,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("wgrad_gemm_accum", &wgrad_gemm_accum);
   m.def("attn_fwd", &attn_fwd);
   m.def("attn_bwd", &attn_bwd);
+  m.def("attn_varlen_fwd", &attn_varlen_fwd);
+  m.def("attn_varlen_bwd", &attn_varlen_bwd);
   m.def("ce_fwd", &ce_fwd);
   m.def("ce_bwd", &ce_bwd);
   m.def("grouped_gemm", &grouped_gemm);

@@ -95,10 +95,8 @@ class SelfAttention(nn.Module):
             self.last_max_logit = max_logits_per_group(q, k, self.softmax_scale)
 
         if packed_seq_params is not None and inference_context is None:
-            from megatron_amd.ops import reference as _ref
-
-            core_out = _ref.attention_varlen(
-                q, k, v, packed_seq_params.cu_seqlens.to(q.device),
+            core_out = ops.flash_attention_varlen(
+                q, k, v, packed_seq_params.cu_seqlens,
                 causal=self.config.causal_attention, scale=self.softmax_scale)
         elif inference_context is not None:
             # the context owns the KV cache and the attention kernel choice

@@ -266,9 +266,9 @@ class MLASelfAttention(nn.Module):
             out, _ = self.linear_proj(core.reshape(s, b, self.nh * self.dv))
             return out
         if packed_seq_params is not None:
-            core = ref.attention_varlen(
+            core = ops.flash_attention_varlen(
                 qf, kf.contiguous(), v.contiguous(),
-                packed_seq_params.cu_seqlens.to(qf.device),
+                packed_seq_params.cu_seqlens,
                 causal=self.config.causal_attention, scale=self.softmax_scale)
         elif self.dqk in (64, 128) and self.dv == self.dqk:
             core = ops.flash_attention(qf, kf.contiguous(), v.contiguous(),

@@ -25,6 +25,7 @@ SRC = [
     "megatron_amd/ops/csrc/causal_conv1d.hip",
     "megatron_amd/ops/csrc/attention_fwd.hip",
     "megatron_amd/ops/csrc/attention_bwd.hip",
+    "megatron_amd/ops/csrc/attention_varlen.hip",
     "megatron_amd/ops/csrc/symm_allreduce.hip",
 ]
 
