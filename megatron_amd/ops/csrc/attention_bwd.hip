@@ -26,6 +26,9 @@
 //   * wave-uniform interior-tile path with no mask arithmetic; only tiles on
 //     the diagonal, the window edge or the ragged tail evaluate the mask.
 //   * per-wave causal/window tile skip; scale folded into one fma per exp.
+// Tile height (KVBLK, also the q tile of dkv), fragment reads and the tile
+// row permutation come from attention_tile.h, shared with the packed kernels
+// (attention_varlen.hip), whose dq/dkv are this file's with another mask.
 #include <torch/extension.h>
 #include <ATen/hip/HIPContext.h>
 #include <type_traits>
@@ -70,7 +73,6 @@ __global__ __launch_bounds__(512) void attn_bwd_dq_kernel(
     const bf16* __restrict__ dout, const float* __restrict__ lse, const float* __restrict__ drow,
     bf16* __restrict__ dq,
     int sq, int skv, int b, int hq, int hkv, float scale, int causal, int window) {
-  constexpr int KVBLK = 64;
   constexpr int QROWS = 16 * QT;  // q rows per wave
   constexpr int ND = D / 16, NKD = D / 32;
   constexpr int KCH = D / 8;
@@ -106,10 +108,8 @@ __global__ __launch_bounds__(512) void attn_bwd_dq_kernel(
     const bf16* dor = dobase + (long)qrow * q_srow;
 #pragma unroll
     for (int kd = 0; kd < NKD; ++kd) {
-      short8 t1 = *reinterpret_cast<const short8*>(qr + kd * 32 + g * 8);
-      qa[qt][kd] = *reinterpret_cast<bf16x8*>(&t1);
-      short8 t2 = *reinterpret_cast<const short8*>(dor + kd * 32 + g * 8);
-      doa[qt][kd] = *reinterpret_cast<bf16x8*>(&t2);
+      qa[qt][kd] = load_frag(qr + kd * 32 + g * 8);
+      doa[qt][kd] = load_frag(dor + kd * 32 + g * 8);
     }
     my_lse_l2[qt] = lse_row[qrow] * LOG2E;
     my_dr_s[qt] = dr_row[qrow] * scale;
@@ -187,10 +187,8 @@ __global__ __launch_bounds__(512) void attn_bwd_dq_kernel(
           int krow = tile_row_a(n, c);
 #pragma unroll
           for (int kd = 0; kd < NKD; ++kd) {
-            short8 t1 = *reinterpret_cast<const short8*>(&K_lds[cur][krow][swz<D>(krow, kd * 4 + g) * 8]);
-            bf16x8 ak = *reinterpret_cast<bf16x8*>(&t1);
-            short8 t2 = *reinterpret_cast<const short8*>(&V_lds[cur][krow][swz<D>(krow, kd * 4 + g) * 8]);
-            bf16x8 av = *reinterpret_cast<bf16x8*>(&t2);
+            bf16x8 ak = read_a<D>(K_lds[cur], krow, kd * 4 + g);
+            bf16x8 av = read_a<D>(V_lds[cur], krow, kd * 4 + g);
 #pragma unroll
             for (int qt = 0; qt < QT; ++qt) {
               st[qt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ak, qa[qt][kd], st[qt], 0, 0, 0);
@@ -278,13 +276,12 @@ __global__ __launch_bounds__(512) void attn_bwd_dkv_kernel(
     const bf16* __restrict__ dout, const float* __restrict__ lse, const float* __restrict__ drow,
     bf16* __restrict__ dk, bf16* __restrict__ dv,
     int sq, int skv, int b, int hq, int hkv, float scale, int causal, int window) {
-  constexpr int QBLK = 64;
   constexpr int ND = D / 16, NKD = D / 32;
   constexpr int KCH = D / 8;
-  constexpr int SREG = QBLK * D / 8 / 512;
+  constexpr int SREG = KVBLK * D / 8 / 512;
 
-  __shared__ __align__(16) short Q_lds[2][QBLK][D];   // row-major, swizzled, double-buffered
-  __shared__ __align__(16) short dO_lds[2][QBLK][D];
+  __shared__ __align__(16) short Q_lds[2][KVBLK][D];   // row-major, swizzled, double-buffered
+  __shared__ __align__(16) short dO_lds[2][KVBLK][D];
 
   const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
   const int g = lane >> 4, c = lane & 15;
@@ -311,10 +308,8 @@ __global__ __launch_bounds__(512) void attn_bwd_dkv_kernel(
     const bf16* vr = vbase + (long)krow * k_srow;
 #pragma unroll
     for (int kd = 0; kd < NKD; ++kd) {
-      short8 t1 = *reinterpret_cast<const short8*>(kr + kd * 32 + g * 8);
-      ka[kd] = *reinterpret_cast<bf16x8*>(&t1);
-      short8 t2 = *reinterpret_cast<const short8*>(vr + kd * 32 + g * 8);
-      va[kd] = *reinterpret_cast<bf16x8*>(&t2);
+      ka[kd] = load_frag(kr + kd * 32 + g * 8);
+      va[kd] = load_frag(vr + kd * 32 + g * 8);
     }
   }
 
@@ -325,9 +320,9 @@ __global__ __launch_bounds__(512) void attn_bwd_dkv_kernel(
     dv_acc[n] = f32x4{0.f, 0.f, 0.f, 0.f};
   }
 
-  int tq_start = causal ? max(0, (k0 - off) / QBLK) : 0;
-  int tq_end = (sq - 1) / QBLK;
-  if (window > 0) tq_end = min(tq_end, (k0 + 127 - off + window - 1) / QBLK);
+  int tq_start = causal ? max(0, (k0 - off) / KVBLK) : 0;
+  int tq_end = (sq - 1) / KVBLK;
+  if (window > 0) tq_end = min(tq_end, (k0 + 127 - off + window - 1) / KVBLK);
 
   int st_row[SREG], st_c8[SREG];
 #pragma unroll
@@ -372,37 +367,35 @@ __global__ __launch_bounds__(512) void attn_bwd_dkv_kernel(
       dr_cu = dr_nx * scale;
     };
 
-    stage_loads(tq_start * QBLK);
+    stage_loads(tq_start * KVBLK);
     stage_writes(0);
     __syncthreads();
 
     for (int t = tq_start; t <= tq_end; ++t) {
-      const int qt0 = t * QBLK;
+      const int qt0 = t * KVBLK;
       const int cur = (t - tq_start) & 1;
       const bool have_next = (t + 1 <= tq_end);
-      if (have_next) stage_loads(qt0 + QBLK);
+      if (have_next) stage_loads(qt0 + KVBLK);
 
       // this wave's kv rows are krow0..+15; skip fully-masked q tiles
-      bool wave_skip = (causal && qt0 + QBLK - 1 < krow0 - off) ||
+      bool wave_skip = (causal && qt0 + KVBLK - 1 < krow0 - off) ||
                        (window > 0 && qt0 >= krow0 + 15 - off + window);
       if (!wave_skip) {
         // no element of this wave's (q tile) x (kv rows) needs the mask
-        const bool interior = (qt0 + QBLK <= sq) && (krow0 + 16 <= skv) &&
+        const bool interior = (qt0 + KVBLK <= sq) && (krow0 + 16 <= skv) &&
                               (!causal || krow0 + 15 <= qt0 + off) &&
-                              (window <= 0 || krow0 > qt0 + QBLK - 1 + off - window);
-        f32x4 st[QBLK / 16], dpt[QBLK / 16];
+                              (window <= 0 || krow0 > qt0 + KVBLK - 1 + off - window);
+        f32x4 st[KVBLK / 16], dpt[KVBLK / 16];
         __builtin_amdgcn_s_setprio(1);
 #pragma unroll
-        for (int n = 0; n < QBLK / 16; ++n) {
+        for (int n = 0; n < KVBLK / 16; ++n) {
           st[n] = f32x4{0.f, 0.f, 0.f, 0.f};
           dpt[n] = f32x4{0.f, 0.f, 0.f, 0.f};
           int qrow = tile_row_a(n, c);
 #pragma unroll
           for (int kd = 0; kd < NKD; ++kd) {
-            short8 t1 = *reinterpret_cast<const short8*>(&Q_lds[cur][qrow][swz<D>(qrow, kd * 4 + g) * 8]);
-            bf16x8 aq = *reinterpret_cast<bf16x8*>(&t1);
-            short8 t2 = *reinterpret_cast<const short8*>(&dO_lds[cur][qrow][swz<D>(qrow, kd * 4 + g) * 8]);
-            bf16x8 ado = *reinterpret_cast<bf16x8*>(&t2);
+            bf16x8 aq = read_a<D>(Q_lds[cur], qrow, kd * 4 + g);
+            bf16x8 ado = read_a<D>(dO_lds[cur], qrow, kd * 4 + g);
             st[n] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(aq, ka[kd], st[n], 0, 0, 0);
             dpt[n] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ado, va[kd], dpt[n], 0, 0, 0);
           }
@@ -410,12 +403,12 @@ __global__ __launch_bounds__(512) void attn_bwd_dkv_kernel(
         __builtin_amdgcn_s_setprio(0);
 
         // P, dS in D-layout [q = tile_row_d(n, g, r)][kv = c]; kv col = krow0 + c
-        int pkP[QBLK / 16][2], pkD[QBLK / 16][2];
+        int pkP[KVBLK / 16][2], pkD[KVBLK / 16][2];
         auto softmax_tile = [&](auto masked_c) {
           constexpr bool MASKED = decltype(masked_c)::value;
           const int kvcol = krow0 + c;
 #pragma unroll
-          for (int n = 0; n < QBLK / 16; ++n) {
+          for (int n = 0; n < KVBLK / 16; ++n) {
             float pv[4], dsv[4];
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
@@ -444,7 +437,7 @@ __global__ __launch_bounds__(512) void attn_bwd_dkv_kernel(
         // dV += P^T dO ; dK += dS^T Q
         __builtin_amdgcn_s_setprio(1);
 #pragma unroll
-        for (int ks2 = 0; ks2 < QBLK / 32; ++ks2) {
+        for (int ks2 = 0; ks2 < KVBLK / 32; ++ks2) {
           bf16x8 aP = own_a_frag(pkP[2 * ks2], pkP[2 * ks2 + 1]);
           bf16x8 aD = own_a_frag(pkD[2 * ks2], pkD[2 * ks2 + 1]);
 #pragma unroll

@@ -1,6 +1,11 @@
 // LDS tile helpers shared by the attention kernels that consume row-major
 // swizzled tiles through A-fragment b128 reads and transposing B-fragment
-// reads (attention_bwd.hip, attention_varlen.hip).
+// reads (attention_bwd.hip, attention_varlen.hip): the tile height KVBLK,
+// fragment reads (load_frag, read_a, read_b_tr, own_a_frag), the row
+// permutation of the first phase, the DPP row broadcast, and the reg-staged
+// tile copy TileStager.  The dense backward still stages with its own
+// lambdas over separate arrays: moving it onto TileStager changes its
+// register allocation (see profiles/README.md).
 #pragma once
 
 #include "common.h"
@@ -11,6 +16,8 @@ typedef short short4v __attribute__((ext_vector_type(4)));
 
 #define LOG2E 1.44269504088896340736f
 #define WAIT_VM0 0x0F70
+
+constexpr int KVBLK = 64;  // rows of a streamed tile (kv rows in fwd/dq, q rows in dkv)
 
 // 16-byte chunk swizzle of a row-major [rows][D] bf16 tile: chunk ^ swzf(row).
 // LDS has 64 four-byte banks, so 256 B (one D=128 row, two D=64 rows) is one
@@ -31,6 +38,57 @@ __device__ __forceinline__ int swzf(int row) {
 }
 template <int D>
 __device__ __forceinline__ int swz(int row, int chunk) { return chunk ^ swzf<D>(row); }
+
+// Reg-staged copy of two [KVBLK][D] row-major tiles (rows x0.. of a and b,
+// row stride `srow` elements, rows >= t read as zero) into swizzled LDS by a
+// 512-thread block: loads() early, writes() late.
+template <int D>
+struct TileStager {
+  static constexpr int KCH = D / 8;
+  static constexpr int SREG = KVBLK * D / 8 / 512;
+  int row[SREG], c8[SREG];
+  short8 ra[SREG], rb[SREG];
+
+  __device__ __forceinline__ TileStager() {
+#pragma unroll
+    for (int i = 0; i < SREG; ++i) {
+      int idx = (int)threadIdx.x + i * 512;
+      row[i] = idx / KCH;
+      c8[i] = idx % KCH;
+    }
+  }
+  __device__ __forceinline__ void loads(const bf16* a, const bf16* b, long srow, int x0, int t) {
+#pragma unroll
+    for (int i = 0; i < SREG; ++i) {
+      const int r = x0 + row[i];
+      ra[i] = short8{0, 0, 0, 0, 0, 0, 0, 0};
+      rb[i] = short8{0, 0, 0, 0, 0, 0, 0, 0};
+      if (r < t) {
+        ra[i] = *reinterpret_cast<const short8*>(a + (long)r * srow + c8[i] * 8);
+        rb[i] = *reinterpret_cast<const short8*>(b + (long)r * srow + c8[i] * 8);
+      }
+    }
+  }
+  __device__ __forceinline__ void writes(short (*A)[D], short (*B)[D]) const {
+#pragma unroll
+    for (int i = 0; i < SREG; ++i) {
+      *reinterpret_cast<short8*>(&A[row[i]][swz<D>(row[i], c8[i]) * 8]) = ra[i];
+      *reinterpret_cast<short8*>(&B[row[i]][swz<D>(row[i], c8[i]) * 8]) = rb[i];
+    }
+  }
+};
+
+// A-fragment (8 bf16) of a first-phase MFMA: 16-byte chunk `chunk` of tile row
+// `row`, and the same from global memory for the register-resident operand.
+template <int D>
+__device__ __forceinline__ bf16x8 read_a(const short (*tile)[D], int row, int chunk) {
+  short8 tmp = *reinterpret_cast<const short8*>(&tile[row][swz<D>(row, chunk) * 8]);
+  return *reinterpret_cast<bf16x8*>(&tmp);
+}
+__device__ __forceinline__ bf16x8 load_frag(const bf16* p) {
+  short8 tmp = *reinterpret_cast<const short8*>(p);
+  return *reinterpret_cast<bf16x8*>(&tmp);
+}
 
 // Transposing LDS read.  Within each group of 16 lanes, lane i supplies the
 // address of 4 consecutive bf16: row i>>2, columns 4(i&3)..+3 of a 4x16

@@ -46,8 +46,6 @@
 
 namespace {
 
-constexpr int KVBLK = 64;  // tile rows of the streamed side, all three kernels
-
 // ---------------------------------------------------------------------------
 // row_lo / row_hi from cu_seqlens, one thread per token.  Token r belongs to
 // document j = #{i in [1, n_docs) : cu[i] <= r}: tokens before cu[0] fall into
@@ -120,55 +118,6 @@ struct WaveBounds {
   __device__ __forceinline__ bool interior(int x0) const { return lo_last <= x0 && hi_first >= x0 + KVBLK; }
   __device__ __forceinline__ bool ok(int i, int x) const { return x >= lo[i] && x < hi[i]; }
 };
-
-// Reg-staged copy of two [KVBLK][D] row-major tiles (rows x0.. of a and b,
-// row stride `srow` elements) into swizzled LDS: loads() early, writes() late.
-template <int D>
-struct TileStager {
-  static constexpr int KCH = D / 8;
-  static constexpr int SREG = KVBLK * D / 8 / 512;
-  int row[SREG], c8[SREG];
-  short8 ra[SREG], rb[SREG];
-
-  __device__ __forceinline__ TileStager() {
-#pragma unroll
-    for (int i = 0; i < SREG; ++i) {
-      int idx = (int)threadIdx.x + i * 512;
-      row[i] = idx / KCH;
-      c8[i] = idx % KCH;
-    }
-  }
-  __device__ __forceinline__ void loads(const bf16* a, const bf16* b, long srow, int x0, int t) {
-#pragma unroll
-    for (int i = 0; i < SREG; ++i) {
-      const int r = x0 + row[i];
-      ra[i] = short8{0, 0, 0, 0, 0, 0, 0, 0};
-      rb[i] = short8{0, 0, 0, 0, 0, 0, 0, 0};
-      if (r < t) {
-        ra[i] = *reinterpret_cast<const short8*>(a + (long)r * srow + c8[i] * 8);
-        rb[i] = *reinterpret_cast<const short8*>(b + (long)r * srow + c8[i] * 8);
-      }
-    }
-  }
-  __device__ __forceinline__ void writes(short (*A)[D], short (*B)[D]) const {
-#pragma unroll
-    for (int i = 0; i < SREG; ++i) {
-      *reinterpret_cast<short8*>(&A[row[i]][swz<D>(row[i], c8[i]) * 8]) = ra[i];
-      *reinterpret_cast<short8*>(&B[row[i]][swz<D>(row[i], c8[i]) * 8]) = rb[i];
-    }
-  }
-};
-
-template <int D>
-__device__ __forceinline__ bf16x8 read_a(const short (*tile)[D], int row, int chunk) {
-  short8 tmp = *reinterpret_cast<const short8*>(&tile[row][swz<D>(row, chunk) * 8]);
-  return *reinterpret_cast<bf16x8*>(&tmp);
-}
-
-__device__ __forceinline__ bf16x8 load_frag(const bf16* p) {
-  short8 tmp = *reinterpret_cast<const short8*>(p);
-  return *reinterpret_cast<bf16x8*>(&tmp);
-}
 
 // ---------------------------------------------------------------------------
 // forward: 8 waves x 32 q rows (256-token blocks), kv tiles of 64.

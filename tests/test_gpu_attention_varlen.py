@@ -50,6 +50,26 @@ def test_varlen_fwd_bwd(lengths, hq, hkv, d, causal):
         assert torch.equal(a, a2), f"{name} differs between two runs"
 
 
+@pytest.mark.parametrize("t,hq,hkv,d,causal", [
+    (200, 4, 2, 128, True),
+    (200, 4, 4, 128, False),
+    (150, 2, 1, 64, True),
+])
+def test_varlen_single_document_is_dense_bwd(t, hq, hkv, d, causal):
+    """A packed batch of one document is the dense layout at b = 1: both
+    backward paths give the same values.  Value equality, not bit patterns: a
+    skipped all-masked tile may leave +0 where the other path leaves -0."""
+    torch.manual_seed(0)
+    q, k, v, dout = (torch.randn(t, 1, h, d, device="cuda", dtype=torch.bfloat16) for h in (hq, hkv, hkv, hq))
+    cu = torch.tensor([0, t], device="cuda", dtype=torch.int32)
+    scale = d ** -0.5
+    out, lse = ops._C.attn_varlen_fwd(q, k, v, cu, causal, scale)
+    dense = ops._C.attn_bwd(dout, q, k, v, out, lse.view(1, hq, t), causal, scale, 0)
+    packed = ops._C.attn_varlen_bwd(dout, q, k, v, out, lse, cu, causal, scale)
+    for name, a, b in zip(NAMES[1:], dense, packed):
+        assert torch.equal(a, b), name
+
+
 def test_varlen_no_leak_across_documents():
     lengths, mid = [70, 90, 60], slice(70, 160)
     cu = torch.tensor([0] + lengths, device="cuda").cumsum(0)
