@@ -26,6 +26,8 @@
 //   * wave-uniform interior-tile path with no mask arithmetic; only tiles on
 //     the diagonal, the window edge or the ragged tail evaluate the mask.
 //   * per-wave causal/window tile skip; scale folded into one fma per exp.
+//   * 1-D grids through attn_block_map (attention_sched.h): whole kv groups
+//     per XCD, the heaviest causal block of every head first.
 // Tile height (KVBLK, also the q tile of dkv), fragment reads and the tile
 // row permutation come from attention_tile.h, shared with the packed kernels
 // (attention_varlen.hip), whose dq/dkv are this file's with another mask.
@@ -33,6 +35,7 @@
 #include <ATen/hip/HIPContext.h>
 #include <type_traits>
 #include "attention_tile.h"
+#include "attention_sched.h"
 
 // ---------------------------------------------------------------------------
 // Drow[b, h, s] = sum_d dO[s,b,h,:] * O[s,b,h,:]
@@ -81,10 +84,12 @@ __global__ __launch_bounds__(512) void attn_bwd_dq_kernel(
   __shared__ __align__(16) short K_lds[2][KVBLK][D];  // row-major, swizzled, double-buffered
   __shared__ __align__(16) short V_lds[2][KVBLK][D];
 
+  const AttnBlock ab = attn_block_map(blockIdx.x, (sq + 8 * QROWS - 1) / (8 * QROWS), b * hkv, hq / hkv, true);
+  if (ab.blk < 0) return;  // padding slot of the grid
   const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
   const int g = lane >> 4, c = lane & 15;
-  const int q0 = blockIdx.x * (8 * QROWS);
-  const int batch = blockIdx.y / hq, head = blockIdx.y % hq;
+  const int q0 = ab.blk * (8 * QROWS);
+  const int batch = ab.head / hq, head = ab.head % hq;
   const int kv_head = head / (hq / hkv);
   const long q_srow = (long)b * hq * D, k_srow = (long)b * hkv * D;
   const bf16* qbase = q + ((long)batch * hq + head) * D;
@@ -283,10 +288,12 @@ __global__ __launch_bounds__(512) void attn_bwd_dkv_kernel(
   __shared__ __align__(16) short Q_lds[2][KVBLK][D];   // row-major, swizzled, double-buffered
   __shared__ __align__(16) short dO_lds[2][KVBLK][D];
 
+  const AttnBlock ab = attn_block_map(blockIdx.x, (skv + 127) / 128, b * hkv, 1, false);
+  if (ab.blk < 0) return;  // padding slot of the grid
   const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
   const int g = lane >> 4, c = lane & 15;
-  const int k0 = blockIdx.x * 128;  // 8 waves x 16 kv rows
-  const int batch = blockIdx.y / hkv, kv_head = blockIdx.y % hkv;
+  const int k0 = ab.blk * 128;  // 8 waves x 16 kv rows
+  const int batch = ab.head / hkv, kv_head = ab.head % hkv;
   const int rep = hq / hkv;
   const long q_srow = (long)b * hq * D, k_srow = (long)b * hkv * D;
   const bf16* kbase = k + ((long)batch * hkv + kv_head) * D;
@@ -525,8 +532,8 @@ std::vector<torch::Tensor> attn_bwd(torch::Tensor dout, torch::Tensor q, torch::
   // via env, for D = 64, or when the sequence is too short to fill 256 rows.
   static const bool force_128 = getenv("MEGATRON_AMD_ATTN_BWD_V2") != nullptr;
   const bool dq_256 = !force_128 && sq >= 256 && d == 128;
-  dim3 grid_dq((sq + (dq_256 ? 255 : 127)) / (dq_256 ? 256 : 128), b * hq);
-  dim3 grid_dkv((skv + 127) / 128, b * hkv);
+  dim3 grid_dq(attn_sched_grid((sq + (dq_256 ? 255 : 127)) / (dq_256 ? 256 : 128), b * hkv, hq / hkv));
+  dim3 grid_dkv(attn_sched_grid((skv + 127) / 128, b * hkv, 1));
   const float fs = (float)scale;
   const int ic = causal ? 1 : 0, iw = (int)window;
   if (d == 128) {

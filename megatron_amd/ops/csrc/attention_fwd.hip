@@ -18,12 +18,14 @@
 //     strides (16B alignment preserved).
 //   * defer-max rescale (T13, THR=8): skip the O/l rescale pass while the
 //     running max grows by < THR (exp headroom is harmless in f32 accum).
-//   * per-wave causal tile skip + block-level tile range; XCD-bijective
-//     workgroup remap so all q-chunks of one (batch,head) share one XCD's L2.
+//   * per-wave causal tile skip + block-level tile range; 1-D grid through
+//     attn_block_map (attention_sched.h): whole kv groups per XCD (one L2 holds
+//     a group's K/V), the heaviest causal q-chunk of every head first.
 //   * s_setprio around MFMA clusters (T5).
 #include <torch/extension.h>
 #include <ATen/hip/HIPContext.h>
 #include "common.h"
+#include "attention_sched.h"
 
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
@@ -54,16 +56,10 @@ __global__ __launch_bounds__(512) void attn_fwd_kernel_v2(
   __shared__ __align__(16) short K_lds[KVBLK][D];      // [kv][d], chunk-swizzled
   __shared__ __align__(16) short Vt_lds[D][KVBLK];     // [d][kv], chunk-swizzled
 
-  // ---- XCD-bijective workgroup remap (T1; bijective per m204) ----
-  const int nwg = gridDim.x;
-  int bid = blockIdx.x;
-  {
-    int q8 = nwg >> 3, r8 = nwg & 7;
-    int xcd = bid & 7, idx = bid >> 3;
-    bid = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + idx;
-  }
-  const int bh = bid / nqc;       // batch * hq + head (contiguous per XCD)
-  const int q0 = (bid % nqc) * QBLK;
+  const AttnBlock ab = attn_block_map(blockIdx.x, nqc, b * hkv, hq / hkv, true);
+  if (ab.blk < 0) return;  // padding slot of the grid
+  const int bh = ab.head;         // batch * hq + head
+  const int q0 = ab.blk * QBLK;
   const int batch = bh / hq;
   const int head = bh % hq;
   const int kv_head = head / (hq / hkv);
@@ -615,7 +611,7 @@ std::vector<torch::Tensor> attn_fwd(torch::Tensor q, torch::Tensor k, torch::Ten
   static const int abl = abl_env ? atoi(abl_env) : 0;
   if (sq >= 256 && !force_v1) {
     int nqc = (sq + 255) / 256;
-    dim3 grid(nqc * b * hq);
+    dim3 grid(attn_sched_grid(nqc, b * hkv, hq / hkv));
     auto launch = [&](auto kern) {
       hipLaunchKernelGGL(kern, grid, dim3(512), 0, stream,
                          (const bf16*)qc.data_ptr(), (const bf16*)kc.data_ptr(), (const bf16*)vc.data_ptr(),

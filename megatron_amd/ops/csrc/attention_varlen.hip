@@ -12,7 +12,11 @@
 //         row_lo[r] <= col < (causal ? r + 1 : row_hi[r]).
 //     Nothing reads cu_seqlens on the host; every grid depends on t only.
 //   * Blocks cover fixed token ranges, whatever the document boundaries are:
-//     there is no work list.  Both bounds are non-decreasing in the row, so
+//     there is no work list.  Every kernel runs on a 1-D grid through
+//     attn_block_map (attention_sched.h): whole kv groups per XCD, blocks in
+//     the order that starts the heaviest causal block of a head first (a
+//     heuristic once documents cut the ramp; the split by head stays exact).
+//     Both bounds are non-decreasing in the row, so
 //     the kv tiles a wave needs are [lo(first row)/64, (hi(last row)-1)/64]
 //     and a block's range is the union over its waves.  A wave skips the MFMA
 //     and softmax work of tiles outside its own range but still stages and
@@ -41,6 +45,7 @@
 #include <ATen/hip/HIPContext.h>
 #include <type_traits>
 #include "attention_tile.h"
+#include "attention_sched.h"
 
 #define RESCALE_THR 8.0f
 
@@ -136,16 +141,10 @@ __global__ __launch_bounds__(512) void attn_varlen_fwd_kernel(
   __shared__ __align__(16) short K_lds[2][KVBLK][D];
   __shared__ __align__(16) short V_lds[2][KVBLK][D];
 
-  // XCD-bijective workgroup remap: one head's q blocks share one XCD's L2
-  int bid = blockIdx.x;
-  {
-    const int nwg = gridDim.x;
-    int q8 = nwg >> 3, r8 = nwg & 7;
-    int xcd = bid & 7, idx = bid >> 3;
-    bid = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + idx;
-  }
-  const int head = bid / nqc;
-  const int q0 = (bid % nqc) * QBLK;
+  const AttnBlock ab = attn_block_map(blockIdx.x, nqc, hkv, hq / hkv, true);
+  if (ab.blk < 0) return;  // padding slot of the grid
+  const int head = ab.head;
+  const int q0 = ab.blk * QBLK;
   const int kv_head = head / (hq / hkv);
 
   const int lane = threadIdx.x & 63;
@@ -358,11 +357,13 @@ __global__ __launch_bounds__(512) void attn_varlen_dq_kernel(
   __shared__ __align__(16) short K_lds[2][KVBLK][D];
   __shared__ __align__(16) short V_lds[2][KVBLK][D];
 
+  const AttnBlock ab = attn_block_map(blockIdx.x, (t + QBLK - 1) / QBLK, hkv, hq / hkv, true);
+  if (ab.blk < 0) return;  // padding slot of the grid
   const int lane = threadIdx.x & 63;
   const int wid = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int g = lane >> 4, c = lane & 15;
-  const int q0 = blockIdx.x * QBLK;
-  const int head = blockIdx.y;
+  const int q0 = ab.blk * QBLK;
+  const int head = ab.head;
   const int kv_head = head / (hq / hkv);
   const long q_srow = (long)hq * D, k_srow = (long)hkv * D;
   const bf16* kbase = k + (long)kv_head * D;
@@ -487,11 +488,13 @@ __global__ __launch_bounds__(512) void attn_varlen_dkv_kernel(
   __shared__ __align__(16) short Q_lds[2][QTILE][D];
   __shared__ __align__(16) short dO_lds[2][QTILE][D];
 
+  const AttnBlock ab = attn_block_map(blockIdx.x, (t + KBLK - 1) / KBLK, hkv, 1, false);
+  if (ab.blk < 0) return;  // padding slot of the grid
   const int lane = threadIdx.x & 63;
   const int wid = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int g = lane >> 4, c = lane & 15;
-  const int k0 = blockIdx.x * KBLK;
-  const int kv_head = blockIdx.y;
+  const int k0 = ab.blk * KBLK;
+  const int kv_head = ab.head;
   const int rep = hq / hkv;
   const long q_srow = (long)hq * D, k_srow = (long)hkv * D;
 
@@ -672,7 +675,7 @@ template <int D>
 void launch_fwd(hipStream_t stream, const torch::Tensor& q, const torch::Tensor& k, const torch::Tensor& v,
                 const int* lo, torch::Tensor& out, torch::Tensor& lse, Shape s, float scale, int causal) {
   const int nqc = (s.t + 255) / 256;
-  hipLaunchKernelGGL((attn_varlen_fwd_kernel<D>), dim3(nqc * s.hq), dim3(512), 0, stream,
+  hipLaunchKernelGGL((attn_varlen_fwd_kernel<D>), dim3(attn_sched_grid(nqc, s.hkv, s.hq / s.hkv)), dim3(512), 0, stream,
                      (const bf16*)q.data_ptr(), (const bf16*)k.data_ptr(), (const bf16*)v.data_ptr(),
                      lo, lo + s.t, (bf16*)out.data_ptr(), lse.data_ptr<float>(),
                      s.t, s.hq, s.hkv, scale, causal, nqc);
@@ -683,11 +686,11 @@ void launch_bwd(hipStream_t stream, const torch::Tensor& q, const torch::Tensor&
                 const torch::Tensor& dout, const torch::Tensor& lse, const torch::Tensor& drow, const int* lo,
                 torch::Tensor& dq, torch::Tensor& dk, torch::Tensor& dv, Shape s, float scale, int causal) {
   const int nblk = (s.t + 127) / 128;
-  hipLaunchKernelGGL((attn_varlen_dq_kernel<D>), dim3(nblk, s.hq), dim3(512), 0, stream,
+  hipLaunchKernelGGL((attn_varlen_dq_kernel<D>), dim3(attn_sched_grid(nblk, s.hkv, s.hq / s.hkv)), dim3(512), 0, stream,
                      (const bf16*)q.data_ptr(), (const bf16*)k.data_ptr(), (const bf16*)v.data_ptr(),
                      (const bf16*)dout.data_ptr(), lse.data_ptr<float>(), drow.data_ptr<float>(),
                      lo, lo + s.t, (bf16*)dq.data_ptr(), s.t, s.hq, s.hkv, scale, causal);
-  hipLaunchKernelGGL((attn_varlen_dkv_kernel<D>), dim3(nblk, s.hkv), dim3(512), 0, stream,
+  hipLaunchKernelGGL((attn_varlen_dkv_kernel<D>), dim3(attn_sched_grid(nblk, s.hkv, 1)), dim3(512), 0, stream,
                      (const bf16*)q.data_ptr(), (const bf16*)k.data_ptr(), (const bf16*)v.data_ptr(),
                      (const bf16*)dout.data_ptr(), lse.data_ptr<float>(), drow.data_ptr<float>(),
                      lo, lo + s.t, (bf16*)dk.data_ptr(), (bf16*)dv.data_ptr(), s.t, s.hq, s.hkv, scale, causal);
