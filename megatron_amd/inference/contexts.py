@@ -9,7 +9,8 @@ so each context picks its kernel:
 * prefill  — contiguous flash attention (hand-written MFMA kernel), new KV
              appended to the cache first,
 * decode   — batched masked attention over per-request lengths (paged gather
-             for the dynamic context).
+             for the dynamic context, or with decode_attention="paged" the
+             HIP split-KV kernel that reads the paged cache in place).
 
 MI355X note: 288 GB HBM3E makes KV capacity cheap — default block size is
 large (256 tokens) to keep block tables small and gathers coalesced.
@@ -231,7 +232,13 @@ class DynamicInferenceContext:
 
     def __init__(self, num_layers: int, num_kv_heads: int, head_dim: int,
                  num_blocks: int = 512, block_size: int = 256,
-                 dtype=torch.bfloat16, device="cuda", kv_cache_dtype=None):
+                 dtype=torch.bfloat16, device="cuda", kv_cache_dtype=None,
+                 decode_attention: str = "gather"):
+        assert decode_attention in ("gather", "paged")
+        # "gather": copy every request's context out of the cache, then fp32
+        # masked attention.  "paged": ops.paged_decode_attention reads the
+        # cache in place through the block tables (HIP kernel on GPU).
+        self.decode_attention = decode_attention
         self.block_size = block_size
         self.num_layers = num_layers
         # physical block 0 is a scratch target for padded rows in hipGraph
@@ -354,6 +361,13 @@ class DynamicInferenceContext:
                  + lens % bs)
         self._store(layer, flat_k, flat_v, slots, k[0], v[0])
         new_lens = lens + 1
+        if self.decode_attention == "paged":
+            # full-width tables in either mode: lengths stay on the device
+            out = ops.paged_decode_attention(
+                q[0], kc, vc, self._block_tables, new_lens, scale,
+                self.k_scale[layer] if self.kv_fp8 else None,
+                self.v_scale[layer] if self.kv_fp8 else None)
+            return out.unsqueeze(0)
         if self._static:
             tables = self._block_tables  # fixed width under graph capture
         else:

@@ -229,6 +229,39 @@ def flash_attention_varlen(q, k, v, cu_seqlens, causal=True, scale=None):
     return ref.attention_varlen(q, k, v, cu_seqlens.to(q.device), causal=causal, scale=scale)
 
 
+def paged_decode_attention(q, k_cache, v_cache, block_tables, context_lens, scale=None,
+                           k_scale=None, v_scale=None):
+    """Decode attention straight off a paged KV cache: q [b, hq, d], k/v cache
+    [num_blocks, block_size, hkv, d] (bf16, or float8_e4m3fn with fp32
+    k/v_scale [num_blocks * block_size, hkv]), block_tables [b, width] int64,
+    context_lens [b] int64 (kv length including the newest token) -> [b, hq, d].
+    Tables and lengths are read on the device only (graph-capturable)."""
+    b, hq, d = q.shape
+    bs, hkv = k_cache.shape[1], k_cache.shape[2]
+    if scale is None:
+        scale = 1.0 / math.sqrt(d)
+    fp8 = k_cache.dtype == torch.float8_e4m3fn
+    # the MFMA kernel tiles for a bf16 query, d in {64, 128}, at most 16 query
+    # heads per kv head and blocks of whole 16-token halves; everything else
+    # (test-size heads, fp32, CPU) takes the plain-PyTorch path
+    if (
+        _use_native(q)
+        and q.dtype == torch.bfloat16
+        and d in (64, 128)
+        and hq % hkv == 0 and hq // hkv <= 16
+        and bs % 16 == 0
+        and v_cache.dtype == k_cache.dtype
+        and (k_cache.dtype == torch.bfloat16 or (fp8 and k_scale is not None and v_scale is not None))
+        and block_tables.dtype == torch.int64 and block_tables.stride(-1) == 1
+        and context_lens.dtype == torch.int64
+    ):
+        return _C.attn_paged_decode(q.contiguous(), k_cache, v_cache, block_tables,
+                                    context_lens.contiguous(), scale,
+                                    k_scale if fp8 else None, v_scale if fp8 else None)
+    return ref.paged_decode_attention(q, k_cache, v_cache, block_tables, context_lens, scale,
+                                      k_scale, v_scale)
+
+
 # ---------------------------------------------------------------------------
 # wgrad GEMM with fp32 accumulation  (K9)
 # ---------------------------------------------------------------------------

@@ -3,7 +3,8 @@
 // reads (attention_bwd.hip, attention_varlen.hip): the tile height KVBLK,
 // fragment reads (load_frag, read_a, read_b_tr, own_a_frag), the row
 // permutation of the first phase, the DPP row broadcast, and the reg-staged
-// tile copy TileStager.  The dense backward still stages with its own
+// tile copy TileStager.  attention_decode.hip uses the swizzle, the row
+// permutation and read_b_tr on wave-private 32-row tiles.  The dense backward still stages with its own
 // lambdas over separate arrays: moving it onto TileStager changes its
 // register allocation (see profiles/README.md).
 #pragma once

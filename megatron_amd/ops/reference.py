@@ -242,6 +242,39 @@ def attention_varlen(
     return out.permute(2, 0, 1, 3).to(q.dtype)
 
 
+def paged_decode_attention(q, k_cache, v_cache, block_tables, context_lens, scale=None,
+                           k_scale=None, v_scale=None):
+    """One-token-per-request attention over a paged KV cache.
+
+    q [b, hq, d]; k/v cache [num_blocks, block_size, hkv, d]; block_tables
+    [b, width]; context_lens [b] (kv length per request); k/v_scale
+    [num_blocks * block_size, hkv] fp32 dequantisation scales of an fp8 cache.
+    Gathers every request's [width * block_size] context, then a masked fp32
+    softmax (slots at or past context_lens[i] may hold anything finite)."""
+    b, hq, d = q.shape
+    bs, hkv = k_cache.shape[1], k_cache.shape[2]
+    rep = hq // hkv
+    if scale is None:
+        scale = 1.0 / math.sqrt(d)
+    slots = (block_tables.unsqueeze(-1) * bs
+             + torch.arange(bs, device=q.device).view(1, 1, bs)).reshape(b, -1)  # [b, L]
+
+    def gather(cache, scales):
+        x = cache.reshape(-1, hkv, d)[slots].float()  # [b, L, hkv, d]
+        if scales is not None:
+            x = x * scales[slots].unsqueeze(-1)
+        return x.permute(0, 2, 1, 3)  # [b, hkv, L, d]
+
+    kf, vf = gather(k_cache, k_scale), gather(v_cache, v_scale)
+    qf = q.float().view(b, hkv, rep, d)
+    scores = torch.einsum("bgrd,bgld->bgrl", qf, kf) * scale  # [b, hkv, rep, L]
+    mask = torch.arange(slots.shape[1], device=q.device)[None, :] >= context_lens[:, None]  # [b, L]
+    scores = scores.masked_fill(mask[:, None, None, :], float("-inf"))
+    probs = torch.softmax(scores, dim=-1)
+    out = torch.einsum("bgrl,bgld->bgrd", probs, vf)
+    return out.reshape(b, hq, d).to(q.dtype)
+
+
 def attention(
     q: torch.Tensor,
     k: torch.Tensor,

@@ -26,6 +26,7 @@ SRC = [
     "megatron_amd/ops/csrc/attention_fwd.hip",
     "megatron_amd/ops/csrc/attention_bwd.hip",
     "megatron_amd/ops/csrc/attention_varlen.hip",
+    "megatron_amd/ops/csrc/attention_decode.hip",
     "megatron_amd/ops/csrc/symm_allreduce.hip",
 ]
 

@@ -28,6 +28,8 @@ def main(argv=None):
     parser.add_argument("--kv-block-size", type=int, default=256)
     parser.add_argument("--kv-cache-dtype", choices=["fp8"], default=None,
                         help="fp8: e4m3 KV payload + per-slot scales (half the cache memory)")
+    parser.add_argument("--decode-attention", choices=["gather", "paged"], default="gather",
+                        help="paged: HIP decode attention straight off the paged cache")
     parser.add_argument("--disable-prefix-caching", action="store_true")
     args = parser.parse_args(argv)
     import os
@@ -49,6 +51,7 @@ def main(argv=None):
     engine = DynamicInferenceEngine(model, tokenizer, num_blocks=args.kv_blocks,
                                     block_size=args.kv_block_size, device=device,
                                     kv_cache_dtype=args.kv_cache_dtype,
+                                    decode_attention=args.decode_attention,
                                     enable_prefix_caching=not args.disable_prefix_caching)
     print(f"serving on {args.host}:{args.port}", flush=True)
     run_server(engine, tokenizer, host=args.host, port=args.port)
