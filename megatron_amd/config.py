@@ -139,6 +139,9 @@ class TransformerConfig(ParallelConfig):
     mamba_d_conv: int = 4
     mamba_expand: int = 2
     mamba_chunk_size: int = 128
+    # SSD scan of the mixer: "torch" (ssm/ssd.py) or "hip" (ops.ssd_chunked_scan /
+    # ops.ssd_step: HIP forward kernels, torch whenever a gradient is needed)
+    mamba_ssd_kernel: str = "torch"
     # hybrid layer allocation: explicit pattern ("M"/"*"/"-") wins over ratios
     hybrid_override_pattern: str = ""
     hybrid_attention_ratio: float = 0.0

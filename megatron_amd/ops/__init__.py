@@ -313,6 +313,61 @@ def causal_conv1d_silu(x: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor
 
 
 # ---------------------------------------------------------------------------
+# Mamba2 SSD scan, forward only  (K14)
+# ---------------------------------------------------------------------------
+
+
+def _ssd_native(x, B, C, D, *others) -> bool:
+    """The HIP scan serves bf16 x/B/C on the GPU with head and state dims in
+    {64, 128}, a per-head D, and no gradient: it has no backward."""
+    tensors = [t for t in (x, B, C, D, *others) if t is not None]
+    return (
+        _use_native(x)
+        and all(t.is_cuda for t in tensors)
+        and x.dtype == B.dtype == C.dtype == torch.bfloat16
+        and x.shape[-1] in (64, 128) and B.shape[-1] in (64, 128)
+        and (D is None or D.dim() == 1)
+        and not (torch.is_grad_enabled() and any(t.requires_grad for t in tensors))
+    )
+
+
+def ssd_chunked_scan(x, dt, A, B, C, D=None, chunk_size=128, initial_state=None,
+                     return_final_state=False):
+    """Chunked SSD scan, same contract as ssm.ssd.ssd_chunked_scan: x [b, l, h, p],
+    dt [b, l, h] (softplus'ed), A [h], B/C [b, l, g, n] -> y [b, l, h, p] (and the
+    final state [b, h, p, n] fp32).  The result does not depend on the chunk
+    length, and the HIP kernels always use chunks of 128 rows: `chunk_size`
+    only steers the torch path.  That path also serves everything the kernels
+    do not: CPU, fp32, other sizes, D [h, p], and any input that needs a
+    gradient."""
+    if _ssd_native(x, B, C, D, dt, A, initial_state) and dt.dtype in (torch.bfloat16, torch.float32):
+        y, final = _C.ssd_scan_fwd(
+            x, dt, A.float(), B, C, None if D is None else D.float(),
+            None if initial_state is None else initial_state.float())
+        return (y, final) if return_final_state else y
+    from megatron_amd.ssm import ssd
+
+    return ssd.ssd_chunked_scan(x, dt, A, B, C, D=D, chunk_size=chunk_size,
+                                initial_state=initial_state, return_final_state=return_final_state)
+
+
+def ssd_step(x, dt, A, B, C, state, D=None):
+    """Single-token SSD update, same contract as ssm.ssd.ssd_step: x [b, h, p],
+    dt [b, h], B/C [b, g, n], state [b, h, p, n] fp32 updated in place ->
+    (y [b, h, p], state).  One HIP kernel reads and writes the state once."""
+    if (
+        _ssd_native(x, B, C, D, dt, A, state)
+        and dt.dtype in (torch.bfloat16, torch.float32)
+        and state.dtype == torch.float32 and state.is_contiguous()
+    ):
+        y = _C.ssd_step_fwd(x, dt, A.float(), B, C, state, None if D is None else D.float())
+        return y, state
+    from megatron_amd.ssm import ssd
+
+    return ssd.ssd_step(x, dt, A, B, C, state, D=D)
+
+
+# ---------------------------------------------------------------------------
 # grouped GEMM for MoE experts  (K11)
 # ---------------------------------------------------------------------------
 

@@ -35,6 +35,11 @@ void grouped_gemm_wgrad(torch::Tensor dy, torch::Tensor x, std::vector<int64_t> 
 std::vector<torch::Tensor> causal_conv1d_fwd(torch::Tensor x, torch::Tensor w, torch::Tensor bias);
 std::vector<torch::Tensor> causal_conv1d_bwd(torch::Tensor dy, torch::Tensor x,
                                              torch::Tensor pre, torch::Tensor w);
+std::vector<torch::Tensor> ssd_scan_fwd(torch::Tensor x, torch::Tensor dt, torch::Tensor A, torch::Tensor B,
+                                        torch::Tensor C, c10::optional<torch::Tensor> D,
+                                        c10::optional<torch::Tensor> initial_state);
+torch::Tensor ssd_step_fwd(torch::Tensor x, torch::Tensor dt, torch::Tensor A, torch::Tensor B, torch::Tensor C,
+                           torch::Tensor state, c10::optional<torch::Tensor> D);
 std::vector<int64_t> symm_ipc_handle(torch::Tensor buf);
 int64_t symm_open_handle(std::vector<int64_t> bytes);
 void symm_close_handle(int64_t ptr);
@@ -64,6 +69,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("grouped_gemm_wgrad", &grouped_gemm_wgrad);
   m.def("causal_conv1d_fwd", &causal_conv1d_fwd);
   m.def("causal_conv1d_bwd", &causal_conv1d_bwd);
+  m.def("ssd_scan_fwd", &ssd_scan_fwd);
+  m.def("ssd_step_fwd", &ssd_step_fwd);
   m.def("symm_ipc_handle", &symm_ipc_handle);
   m.def("symm_open_handle", &symm_open_handle);
   m.def("symm_close_handle", &symm_close_handle);

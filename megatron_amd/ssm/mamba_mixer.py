@@ -9,7 +9,9 @@ row-wise in out_proj, exactly mirroring the reference's sharding contract
 inside the mixer.
 
 MI355X notes: the SSD scan (ssm/ssd.py) is all batched GEMMs -> MFMA via
-rocBLAS; the conv is a depthwise F.conv1d (MIOpen); state math is fp32.
+rocBLAS, or with config.mamba_ssd_kernel="hip" the forward kernels of
+ops/csrc/ssd_scan.hip whenever no gradient is needed; the conv is the HIP
+causal_conv1d kernel (F.conv1d fallback); state math is fp32.
 Decode keeps a rolling conv window and an fp32 SSM state per request
 (reference's inference_params conv_state/ssm_state contract).
 """
@@ -69,6 +71,15 @@ class MambaMixer(nn.Module):
             "Mamba TP shards heads and groups: need nheads % tp == 0 and ngroups % tp == 0"
         )
         self.chunk_size = config.mamba_chunk_size
+        kernel = getattr(config, "mamba_ssd_kernel", "torch")
+        if kernel not in ("torch", "hip"):
+            raise ValueError(f"mamba_ssd_kernel must be 'torch' or 'hip', got {kernel!r}")
+        if kernel == "hip":
+            from megatron_amd import ops
+
+            self._scan, self._scan_step = ops.ssd_chunked_scan, ops.ssd_step
+        else:
+            self._scan, self._scan_step = ssd_chunked_scan, ssd_step
 
         self.d_inner_local = self.d_inner // tp
         self.nheads_local = self.nheads // tp
@@ -189,11 +200,11 @@ class MambaMixer(nn.Module):
         A = -torch.exp(self.A_log)
 
         if inference_state is not None:
-            y, final = ssd_chunked_scan(x, dtv.to(x.dtype), A, B, C, D=self.D,
-                                        chunk_size=self.chunk_size, return_final_state=True)
+            y, final = self._scan(x, dtv.to(x.dtype), A, B, C, D=self.D,
+                                  chunk_size=self.chunk_size, return_final_state=True)
             inference_state["ssm"].copy_(final)
         else:
-            y = ssd_chunked_scan(x, dtv.to(x.dtype), A, B, C, D=self.D, chunk_size=self.chunk_size)
+            y = self._scan(x, dtv.to(x.dtype), A, B, C, D=self.D, chunk_size=self.chunk_size)
 
         y = y.reshape(b, s, self.d_inner_local).permute(1, 0, 2)  # [s, b, d_inner/tp]
         y = self.norm(y, z)
@@ -249,8 +260,8 @@ class MambaMixer(nn.Module):
         hsel = torch.arange(r * nh, (r + 1) * nh, device=device)
         dtv = F.softplus(dtf.permute(1, 0, 2).float() + self.dt_bias.index_select(0, hsel))
         A = -torch.exp(self.A_log.index_select(0, hsel))
-        y = ssd_chunked_scan(xs, dtv.to(xs.dtype), A, Bs, Cs,
-                             D=self.D.index_select(0, hsel), chunk_size=self.chunk_size)
+        y = self._scan(xs, dtv.to(xs.dtype), A, Bs, Cs,
+                       D=self.D.index_select(0, hsel), chunk_size=self.chunk_size)
         y = y.reshape(b, s, nh * self.headdim).permute(1, 0, 2)  # [s_full, b, d_inner/(tp*cp)]
         y = cp_channel_to_seq(y, mode=cp_mode)              # [s_loc, b, d_inner/tp]
         y = self.norm(y, z)
@@ -274,7 +285,7 @@ class MambaMixer(nn.Module):
         Cs = Cs.view(b, self.ngroups_local, self.d_state)
         dts = F.softplus(dt[0].float() + self.dt_bias)  # [b, h]
         A = -torch.exp(self.A_log)
-        y, _ = ssd_step(xs, dts.to(xs.dtype), A, Bs, Cs, state["ssm"], D=self.D)
+        y, _ = self._scan_step(xs, dts.to(xs.dtype), A, Bs, Cs, state["ssm"], D=self.D)
         y = y.reshape(1, b, self.d_inner_local)
         y = self.norm(y, z)
         out, _ = self.out_proj(y)

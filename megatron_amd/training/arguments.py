@@ -56,6 +56,9 @@ def build_arg_parser() -> argparse.ArgumentParser:
     g.add_argument("--mamba-state-dim", type=int, default=128)
     g.add_argument("--mamba-head-dim", type=int, default=64)
     g.add_argument("--mamba-num-groups", type=int, default=8)
+    g.add_argument("--mamba-ssd-kernel", choices=["torch", "hip"], default="torch",
+                   help="SSD scan of the Mamba mixer: torch ops, or the HIP forward kernels "
+                        "(torch still runs whenever a gradient is needed)")
     g.add_argument("--hybrid-override-pattern", type=str, default="")
     g.add_argument("--hybrid-attention-ratio", type=float, default=0.0)
     g.add_argument("--hybrid-mlp-ratio", type=float, default=0.0)
@@ -323,6 +326,7 @@ def configs_from_args(args):
         mamba_state_dim=args.mamba_state_dim,
         mamba_head_dim=args.mamba_head_dim,
         mamba_num_groups=args.mamba_num_groups,
+        mamba_ssd_kernel=args.mamba_ssd_kernel,
         hybrid_override_pattern=args.hybrid_override_pattern,
         hybrid_attention_ratio=args.hybrid_attention_ratio,
         hybrid_mlp_ratio=args.hybrid_mlp_ratio,
