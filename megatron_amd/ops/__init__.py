@@ -45,6 +45,13 @@ def _use_native(x: torch.Tensor) -> bool:
     return True
 
 
+def unfused_glue() -> bool:
+    """MEGATRON_AMD_UNFUSED_GLUE=1 (read per call): attention and the layer
+    compose split + rope_apply and bias_dropout_add + rms_norm from the
+    separate ops instead of the fused kernels (A/B runs, bitwise tests)."""
+    return os.environ.get("MEGATRON_AMD_UNFUSED_GLUE", "0") == "1"
+
+
 # ---------------------------------------------------------------------------
 # RMSNorm  (K3)
 # ---------------------------------------------------------------------------
@@ -70,6 +77,34 @@ def rms_norm(x: torch.Tensor, weight: torch.Tensor, eps: float) -> torch.Tensor:
     if _use_native(x):
         return _RMSNormFn.apply(x.contiguous(), weight, eps)
     return ref.rms_norm(x, weight, eps)
+
+
+class _AddRMSNormFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, residual, weight, eps):
+        h = x.shape[-1]
+        total, normed, rstd = _C.add_rmsnorm_fwd(x.reshape(-1, h), residual.reshape(-1, h), weight, eps)
+        ctx.save_for_backward(total, weight, rstd)
+        return total.view_as(x), normed.view_as(x)
+
+    @staticmethod
+    def backward(ctx, dsum, dnormed):
+        total, weight, rstd = ctx.saved_tensors
+        h = total.shape[-1]
+        dx, dw = _C.rmsnorm_bwd(dnormed.contiguous().reshape(-1, h), total, weight, rstd,
+                                dsum.contiguous().reshape(-1, h))
+        dx = dx.view_as(dsum)
+        return dx, dx, dw, None
+
+
+def add_rms_norm(x: torch.Tensor, residual: torch.Tensor, weight: torch.Tensor, eps: float):
+    """(residual + x, rms_norm(residual + x)) in one kernel; the backward folds
+    the sum's own gradient into the norm's dx.  Same bits as bias_dropout_add
+    followed by rms_norm."""
+    if _use_native(x) and x.dtype == torch.bfloat16 and residual.shape == x.shape:
+        return _AddRMSNormFn.apply(x.contiguous(), residual.contiguous(), weight, eps)
+    total = residual + x
+    return total, rms_norm(total, weight, eps)
 
 
 # ---------------------------------------------------------------------------
@@ -153,6 +188,39 @@ def rope_apply(x: torch.Tensor, freqs: torch.Tensor) -> torch.Tensor:
         cos, sin = rope_cos_sin(freqs)
         return _RopeFn.apply(x.contiguous(), cos, sin)
     return ref.rope_apply(x, freqs)
+
+
+class _QKVSplitRopeFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, qkv, cos, sin, rep):
+        ctx.save_for_backward(cos, sin)
+        q, k, v = _C.qkv_split_rope_fwd(qkv, cos, sin, rep)
+        return q, k, v
+
+    @staticmethod
+    def backward(ctx, dq, dk, dv):
+        cos, sin = ctx.saved_tensors
+        return _C.qkv_split_rope_bwd(dq, dk, dv, cos, sin), None, None, None
+
+
+def qkv_split_rope_fused(qkv: torch.Tensor, freqs: Optional[torch.Tensor], rep: int) -> bool:
+    """Whether qkv_split_rope takes the fused kernel for these inputs."""
+    if freqs is None or freqs.dim() != 2 or qkv.dtype != torch.bfloat16 or unfused_glue():
+        return False
+    if freqs.dtype != torch.float32 or freqs.shape[0] != qkv.shape[0]:
+        return False
+    d = qkv.shape[-1] // (rep + 2)
+    half = freqs.shape[-1]
+    return d % 8 == 0 and half % 8 == 0 and 2 * half <= d and _use_native(qkv)
+
+
+def qkv_split_rope(qkv: torch.Tensor, freqs: torch.Tensor, rep: int):
+    """qkv [s,b,ng,(rep+2)*d] (per group: rep q heads | k | v), freqs [s, d_rot/2]
+    -> contiguous q [s,b,ng*rep,d], k, v [s,b,ng,d] with rotate-half RoPE on q
+    and k, in one pass; one pass back for the packed gradient.  Callers check
+    qkv_split_rope_fused first."""
+    cos, sin = rope_cos_sin(freqs)
+    return _QKVSplitRopeFn.apply(qkv.contiguous(), cos, sin, rep)
 
 
 # ---------------------------------------------------------------------------

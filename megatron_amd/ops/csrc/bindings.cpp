@@ -2,11 +2,16 @@
 #include <torch/extension.h>
 
 std::vector<torch::Tensor> rmsnorm_fwd(torch::Tensor x, torch::Tensor w, double eps);
-std::vector<torch::Tensor> rmsnorm_bwd(torch::Tensor dy, torch::Tensor x, torch::Tensor w, torch::Tensor rstd);
+std::vector<torch::Tensor> rmsnorm_bwd(torch::Tensor dy, torch::Tensor x, torch::Tensor w, torch::Tensor rstd,
+                                       c10::optional<torch::Tensor> dres);
+std::vector<torch::Tensor> add_rmsnorm_fwd(torch::Tensor x, torch::Tensor residual, torch::Tensor w, double eps);
 torch::Tensor swiglu_fwd(torch::Tensor x);
 torch::Tensor swiglu_bwd(torch::Tensor dy, torch::Tensor x);
 torch::Tensor rope_fwd(torch::Tensor x, torch::Tensor cost, torch::Tensor sint);
 torch::Tensor rope_bwd(torch::Tensor dy, torch::Tensor cost, torch::Tensor sint);
+std::vector<torch::Tensor> qkv_split_rope_fwd(torch::Tensor qkv, torch::Tensor cost, torch::Tensor sint, long rep);
+torch::Tensor qkv_split_rope_bwd(torch::Tensor dq, torch::Tensor dk, torch::Tensor dv,
+                                 torch::Tensor cost, torch::Tensor sint);
 void multi_tensor_adamw(std::vector<torch::Tensor> params, std::vector<torch::Tensor> grads,
                         std::vector<torch::Tensor> exp_avgs, std::vector<torch::Tensor> exp_avg_sqs,
                         std::vector<torch::Tensor> model_params,
@@ -49,11 +54,15 @@ void symm_allreduce(std::vector<int64_t> peer_ptrs, int64_t payload_bytes,
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("rmsnorm_fwd", &rmsnorm_fwd);
-  m.def("rmsnorm_bwd", &rmsnorm_bwd);
+  m.def("rmsnorm_bwd", &rmsnorm_bwd, pybind11::arg("dy"), pybind11::arg("x"), pybind11::arg("w"),
+        pybind11::arg("rstd"), pybind11::arg("dres") = pybind11::none());
+  m.def("add_rmsnorm_fwd", &add_rmsnorm_fwd);
   m.def("swiglu_fwd", &swiglu_fwd);
   m.def("swiglu_bwd", &swiglu_bwd);
   m.def("rope_fwd", &rope_fwd);
   m.def("rope_bwd", &rope_bwd);
+  m.def("qkv_split_rope_fwd", &qkv_split_rope_fwd);
+  m.def("qkv_split_rope_bwd", &qkv_split_rope_bwd);
   m.def("multi_tensor_adamw", &multi_tensor_adamw);
   m.def("multi_tensor_l2norm", &multi_tensor_l2norm);
   m.def("wgrad_gemm_accum", &wgrad_gemm_accum);

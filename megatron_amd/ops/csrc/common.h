@@ -52,6 +52,20 @@ __device__ __forceinline__ int pack_bf16x2(float lo, float hi) {
   return __builtin_bit_cast(int, h);
 }
 
+// fp32 multiply, add and fused multiply-add that stay what they say: the
+// products and sums are outside the compiler's contraction (which fuses or not
+// depending on the code around an expression), for kernels that must agree
+// with another kernel to the bit.
+__device__ __forceinline__ float mul_rn(float a, float b) {
+#pragma clang fp contract(off)
+  return a * b;
+}
+__device__ __forceinline__ float add_rn(float a, float b) {
+#pragma clang fp contract(off)
+  return a + b;
+}
+__device__ __forceinline__ float fma_rn(float a, float b, float c) { return __builtin_fmaf(a, b, c); }
+
 // full-wave reduction (64 lanes)
 __device__ __forceinline__ float wave_reduce_sum(float v) {
 #pragma unroll

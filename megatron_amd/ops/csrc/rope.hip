@@ -6,6 +6,7 @@
 #include <torch/extension.h>
 #include <ATen/hip/HIPContext.h>
 #include "common.h"
+#include "rope_math.h"
 
 template <bool BWD>
 __global__ void rope_kernel(const bf16* __restrict__ x, const float* __restrict__ cost,
@@ -25,9 +26,10 @@ __global__ void rope_kernel(const bf16* __restrict__ x, const float* __restrict_
     for (int i = lane; i < half; i += WAVE) {
       float x1 = bf2f(xr[i]);
       float x2 = bf2f(xr[i + half]);
-      float cv = c[i], sv = BWD ? -sn[i] : sn[i];
-      orow[i] = f2bf(x1 * cv - x2 * sv);
-      orow[i + half] = f2bf(x2 * cv + x1 * sv);
+      float o1, o2;
+      rope_rotate<BWD>(x1, x2, c[i], sn[i], o1, o2);
+      orow[i] = f2bf(o1);
+      orow[i + half] = f2bf(o2);
     }
     for (int i = 2 * half + lane; i < d; i += WAVE) orow[i] = xr[i];
   }

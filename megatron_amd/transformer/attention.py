@@ -76,18 +76,22 @@ class SelfAttention(nn.Module):
         d = self.kv_channels
         # fused-QKV layout: per query group [rep*d q | d k | d v] (reference attention.py GQA split)
         qkv = qkv.view(s, b, ng, (rep + 2) * d)
-        q, k, v = torch.split(qkv, [rep * d, d, d], dim=3)
-        q = q.reshape(s, b, ng * rep, d)
-        k = k.reshape(s, b, ng, d)
-        v = v.reshape(s, b, ng, d)
+        if self.q_layernorm is None and ops.qkv_split_rope_fused(qkv, rotary_freqs, rep):
+            # split, RoPE on q and k, and contiguous q/k/v in one kernel
+            q, k, v = ops.qkv_split_rope(qkv, rotary_freqs, rep)
+        else:
+            q, k, v = torch.split(qkv, [rep * d, d, d], dim=3)
+            q = q.reshape(s, b, ng * rep, d)
+            k = k.reshape(s, b, ng, d)
+            v = v.reshape(s, b, ng, d)
 
-        if self.q_layernorm is not None:
-            q = ops.rms_norm(q, self.q_layernorm, self.config.layernorm_epsilon)
-            k = ops.rms_norm(k, self.k_layernorm, self.config.layernorm_epsilon)
+            if self.q_layernorm is not None:
+                q = ops.rms_norm(q, self.q_layernorm, self.config.layernorm_epsilon)
+                k = ops.rms_norm(k, self.k_layernorm, self.config.layernorm_epsilon)
 
-        if rotary_freqs is not None:
-            q = ops.rope_apply(q, rotary_freqs)
-            k = ops.rope_apply(k, rotary_freqs)
+            if rotary_freqs is not None:
+                q = ops.rope_apply(q, rotary_freqs)
+                k = ops.rope_apply(k, rotary_freqs)
 
         if getattr(self.config, "qk_clip_threshold", None) and self.training:
             from megatron_amd.optimizer.qk_clip import max_logits_per_group

@@ -103,9 +103,17 @@ class TransformerLayer(nn.Module):
         x = self.self_attention(x, rotary_freqs=rotary_freqs, attention_mask=attention_mask,
                                 inference_context=inference_context, packed_seq_params=packed_seq_params,
                                 **kw)
-        x = ops.bias_dropout_add(x, None, residual, self.hidden_dropout, self.training)
+        norm = self.pre_mlp_layernorm
+        if (type(norm) is Norm and norm.kind == "rmsnorm"
+                and (self.hidden_dropout == 0.0 or not self.training)
+                and x.is_cuda and x.dtype == torch.bfloat16 and residual.dtype == torch.bfloat16
+                and not ops.unfused_glue()):
+            # residual add and pre-MLP norm in one kernel, one fused gradient back
+            x, y = ops.add_rms_norm(x, residual, norm.weight, norm.eps)
+        else:
+            x = ops.bias_dropout_add(x, None, residual, self.hidden_dropout, self.training)
+            y = norm(x)
         residual = x
-        y = self.pre_mlp_layernorm(x)
         if (self.config.recompute_granularity == "selective" and self.training
                 and any(m in ("mlp", "moe") for m in (self.config.recompute_modules or []))):
             # module-level recompute (reference --recompute-modules): the

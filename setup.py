@@ -18,6 +18,7 @@ SRC = [
     "megatron_amd/ops/csrc/rmsnorm.hip",
     "megatron_amd/ops/csrc/swiglu.hip",
     "megatron_amd/ops/csrc/rope.hip",
+    "megatron_amd/ops/csrc/qkv_rope.hip",
     "megatron_amd/ops/csrc/adamw.hip",
     "megatron_amd/ops/csrc/wgrad.hip",
     "megatron_amd/ops/csrc/cross_entropy.hip",
