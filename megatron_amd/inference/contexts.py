@@ -7,7 +7,9 @@ attention over it. The attention module calls ``context.attend(layer, q, k, v)``
 so each context picks its kernel:
 
 * prefill  — contiguous flash attention (hand-written MFMA kernel), new KV
-             appended to the cache first,
+             appended to the cache first (a chunk that reads the cache gathers
+             it first, or with prefill_attention="paged" the HIP kernel reads
+             the paged cache in place),
 * decode   — batched masked attention over per-request lengths (paged gather
              for the dynamic context, or with decode_attention="paged" the
              HIP split-KV kernel that reads the paged cache in place).
@@ -233,12 +235,18 @@ class DynamicInferenceContext:
     def __init__(self, num_layers: int, num_kv_heads: int, head_dim: int,
                  num_blocks: int = 512, block_size: int = 256,
                  dtype=torch.bfloat16, device="cuda", kv_cache_dtype=None,
-                 decode_attention: str = "gather"):
+                 decode_attention: str = "gather", prefill_attention: str = "gather"):
         assert decode_attention in ("gather", "paged")
+        assert prefill_attention in ("gather", "paged")
         # "gather": copy every request's context out of the cache, then fp32
         # masked attention.  "paged": ops.paged_decode_attention reads the
         # cache in place through the block tables (HIP kernel on GPU).
         self.decode_attention = decode_attention
+        # the same choice for a prefill chunk that has to read the cache (one
+        # that starts past position 0, or any chunk of an fp8 cache):
+        # "gather" copies (and dequantises) the whole context, then dense
+        # flash attention; "paged": ops.paged_prefill_attention reads it in place.
+        self.prefill_attention = prefill_attention
         self.block_size = block_size
         self.num_layers = num_layers
         # physical block 0 is a scratch target for padded rows in hipGraph
@@ -343,6 +351,12 @@ class DynamicInferenceContext:
             self._store(layer, flat_k, flat_v, slots, k[:, 0], v[:, 0])
             if self._prior_len == 0 and not self.kv_fp8:
                 return ops.flash_attention(q, k, v, causal=True, scale=scale, window=window)
+            if self.prefill_attention == "paged":
+                out = ops.paged_prefill_attention(
+                    q[:, 0], kc, vc, self._prefill_table, self._prior_len, scale, window,
+                    self.k_scale[layer] if self.kv_fp8 else None,
+                    self.v_scale[layer] if self.kv_fp8 else None)
+                return out.unsqueeze(1)
             # chunked prefill: gather prior + current contiguous KV.  (fp8
             # mode reads back even fresh writes so prefill and decode see the
             # SAME quantized values — keeps the two paths consistent.)

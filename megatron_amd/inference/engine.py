@@ -377,7 +377,7 @@ class DynamicInferenceEngine:
                  max_batch: int = 64, max_prefill_tokens: int = 8192, device=None,
                  use_hip_graphs: bool = True, enable_prefix_caching: bool = True,
                  kv_cache_dtype=None, scheduling_policy: str = "fcfs",
-                 decode_attention: str = "gather"):
+                 decode_attention: str = "gather", prefill_attention: str = "gather"):
         self.model = model.eval()
         self.tokenizer = tokenizer
         cfg = model.config
@@ -390,7 +390,7 @@ class DynamicInferenceEngine:
             (cfg.num_query_groups or cfg.num_attention_heads) // tp,
             cfg.kv_channels, num_blocks=num_blocks, block_size=block_size,
             dtype=cfg.params_dtype, device=device, kv_cache_dtype=kv_cache_dtype,
-            decode_attention=decode_attention)
+            decode_attention=decode_attention, prefill_attention=prefill_attention)
         self.max_batch = max_batch
         self.max_prefill_tokens = max_prefill_tokens
         assert scheduling_policy in ("fcfs", "priority", "sjf")

@@ -330,6 +330,41 @@ def paged_decode_attention(q, k_cache, v_cache, block_tables, context_lens, scal
                                       k_scale, v_scale)
 
 
+def paged_prefill_attention(q, k_cache, v_cache, block_table, prior_len, scale=None, window=None,
+                            k_scale=None, v_scale=None):
+    """Prefill attention of one request straight off a paged KV cache: q
+    [s, hq, d] at positions prior_len .. prior_len + s - 1, k/v cache
+    [num_blocks, block_size, hkv, d] (bf16, or float8_e4m3fn with fp32
+    k/v_scale [num_blocks * block_size, hkv]) already holding positions
+    0 .. prior_len + s - 1, block_table [width] int64 -> [s, hq, d].  Causal
+    with offset, optional sliding window.  prior_len is a host int."""
+    s, hq, d = q.shape
+    bs, hkv = k_cache.shape[1], k_cache.shape[2]
+    if scale is None:
+        scale = 1.0 / math.sqrt(d)
+    fp8 = k_cache.dtype == torch.float8_e4m3fn
+    # the MFMA kernel tiles for a bf16 query, d in {64, 128} and blocks of
+    # whole 16-token halves; everything else (test-size heads, fp32, CPU)
+    # takes the plain-PyTorch path
+    if (
+        _use_native(q)
+        and q.dtype == torch.bfloat16
+        and d in (64, 128)
+        and hq % hkv == 0
+        and bs % 16 == 0
+        and v_cache.dtype == k_cache.dtype
+        and (k_cache.dtype == torch.bfloat16 or (fp8 and k_scale is not None and v_scale is not None))
+        and block_table.dtype == torch.int64 and block_table.dim() == 1
+        and prior_len + s <= block_table.shape[0] * bs
+        and (window is None or window >= 1)
+    ):
+        return _C.attn_paged_prefill(q.contiguous(), k_cache, v_cache, block_table.contiguous(),
+                                     int(prior_len), scale, window if window is not None else 0,
+                                     k_scale if fp8 else None, v_scale if fp8 else None)
+    return ref.paged_prefill_attention(q, k_cache, v_cache, block_table, prior_len, scale, window,
+                                       k_scale, v_scale)
+
+
 # ---------------------------------------------------------------------------
 # wgrad GEMM with fp32 accumulation  (K9)
 # ---------------------------------------------------------------------------

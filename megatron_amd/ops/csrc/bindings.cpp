@@ -31,6 +31,9 @@ std::vector<torch::Tensor> attn_varlen_bwd(torch::Tensor dout, torch::Tensor q, 
 torch::Tensor attn_paged_decode(torch::Tensor q, torch::Tensor k_cache, torch::Tensor v_cache,
                                 torch::Tensor block_tables, torch::Tensor lens, double scale,
                                 c10::optional<torch::Tensor> k_scale, c10::optional<torch::Tensor> v_scale);
+torch::Tensor attn_paged_prefill(torch::Tensor q, torch::Tensor k_cache, torch::Tensor v_cache,
+                                 torch::Tensor block_table, long prior_len, double scale, long window,
+                                 c10::optional<torch::Tensor> k_scale, c10::optional<torch::Tensor> v_scale);
 std::vector<torch::Tensor> ce_fwd(torch::Tensor logits, torch::Tensor target, long vocab_start);
 void ce_bwd(torch::Tensor logits, torch::Tensor target, torch::Tensor row_max,
             torch::Tensor row_inv_sumexp, torch::Tensor grad_out, long vocab_start);
@@ -71,6 +74,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("attn_varlen_fwd", &attn_varlen_fwd);
   m.def("attn_varlen_bwd", &attn_varlen_bwd);
   m.def("attn_paged_decode", &attn_paged_decode);
+  m.def("attn_paged_prefill", &attn_paged_prefill);
   m.def("ce_fwd", &ce_fwd);
   m.def("ce_bwd", &ce_bwd);
   m.def("grouped_gemm", &grouped_gemm);

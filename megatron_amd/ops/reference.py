@@ -275,6 +275,31 @@ def paged_decode_attention(q, k_cache, v_cache, block_tables, context_lens, scal
     return out.reshape(b, hq, d).to(q.dtype)
 
 
+def paged_prefill_attention(q, k_cache, v_cache, block_table, prior_len, scale=None, window=None,
+                            k_scale=None, v_scale=None):
+    """One request's prefill chunk over a paged KV cache.
+
+    q [s, hq, d] at positions prior_len .. prior_len + s - 1; k/v cache
+    [num_blocks, block_size, hkv, d]; block_table [width]; k/v_scale
+    [num_blocks * block_size, hkv] fp32 dequantisation scales of an fp8 cache.
+    Gathers positions 0 .. prior_len + s - 1 through the table (an fp8 cache
+    is dequantised to q's dtype), then causal attention with offset."""
+    s = q.shape[0]
+    bs, hkv, d = k_cache.shape[1], k_cache.shape[2], k_cache.shape[3]
+    pos = torch.arange(prior_len + s, device=q.device)
+    slots = block_table[torch.div(pos, bs, rounding_mode="floor")] * bs + pos % bs
+
+    def gather(cache, scales):
+        x = cache.reshape(-1, hkv, d)[slots]
+        if scales is not None:
+            x = (x.float() * scales[slots].unsqueeze(-1)).to(q.dtype)
+        return x.unsqueeze(1)  # [L, 1, hkv, d]
+
+    out = attention(q.unsqueeze(1), gather(k_cache, k_scale), gather(v_cache, v_scale),
+                    causal=True, scale=scale, window=window)
+    return out[:, 0]
+
+
 def attention(
     q: torch.Tensor,
     k: torch.Tensor,

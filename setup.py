@@ -29,6 +29,7 @@ SRC = [
     "megatron_amd/ops/csrc/attention_bwd.hip",
     "megatron_amd/ops/csrc/attention_varlen.hip",
     "megatron_amd/ops/csrc/attention_decode.hip",
+    "megatron_amd/ops/csrc/attention_prefill_paged.hip",
     "megatron_amd/ops/csrc/symm_allreduce.hip",
 ]
 

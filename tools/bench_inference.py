@@ -37,6 +37,8 @@ def main(argv=None):
     p.add_argument("--kv-cache-dtype", choices=["fp8"], default=None)
     p.add_argument("--decode-attention", choices=["gather", "paged"], default="gather",
                    help="paged: HIP decode attention straight off the paged cache")
+    p.add_argument("--prefill-attention", choices=["gather", "paged"], default="gather",
+                   help="paged: HIP prefill attention straight off the paged cache")
     p.add_argument("--speculative", action="store_true",
                    help="static-engine draft-verify decode (prompt-lookup drafts)")
     args = p.parse_args(argv)
@@ -56,7 +58,8 @@ def main(argv=None):
     num_blocks = (max_tokens_total + args.block_size - 1) // args.block_size
     eng = DynamicInferenceEngine(model, num_blocks=num_blocks, block_size=args.block_size,
                                  max_batch=args.batch, kv_cache_dtype=args.kv_cache_dtype,
-                                 decode_attention=args.decode_attention)
+                                 decode_attention=args.decode_attention,
+                                 prefill_attention=args.prefill_attention)
     rng = torch.Generator().manual_seed(0)
     prompts = [torch.randint(0, args.vocab, (args.isl,), generator=rng).tolist()
                for _ in range(args.batch)]
@@ -84,7 +87,7 @@ def main(argv=None):
         "elapsed_s": round(dt, 2), "batch": args.batch, "isl": args.isl, "osl": args.osl,
         "params_m": round(n_params / 1e6, 1), "dtype": "bf16", "data": "synthetic",
         "kv_cache_dtype": args.kv_cache_dtype or "bf16", "speculative": args.speculative,
-        "decode_attention": args.decode_attention,
+        "decode_attention": args.decode_attention, "prefill_attention": args.prefill_attention,
     }))
 
 

@@ -30,6 +30,8 @@ def main(argv=None):
                         help="fp8: e4m3 KV payload + per-slot scales (half the cache memory)")
     parser.add_argument("--decode-attention", choices=["gather", "paged"], default="gather",
                         help="paged: HIP decode attention straight off the paged cache")
+    parser.add_argument("--prefill-attention", choices=["gather", "paged"], default="gather",
+                        help="paged: HIP prefill attention straight off the paged cache")
     parser.add_argument("--disable-prefix-caching", action="store_true")
     args = parser.parse_args(argv)
     import os
@@ -52,6 +54,7 @@ def main(argv=None):
                                     block_size=args.kv_block_size, device=device,
                                     kv_cache_dtype=args.kv_cache_dtype,
                                     decode_attention=args.decode_attention,
+                                    prefill_attention=args.prefill_attention,
                                     enable_prefix_caching=not args.disable_prefix_caching)
     print(f"serving on {args.host}:{args.port}", flush=True)
     run_server(engine, tokenizer, host=args.host, port=args.port)
