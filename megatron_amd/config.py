@@ -105,6 +105,10 @@ class TransformerConfig(ParallelConfig):
     moe_router_pre_softmax: bool = False
     moe_shared_expert_intermediate_size: Optional[int] = None
     moe_grouped_gemm: bool = True
+    # expert GEMMs: "torch" (torch._grouped_mm, one host read of the expert sizes
+    # per layer) or "hip" (ops/csrc/grouped_gemm_hip.hip: sizes stay on the
+    # device, fp32 wgrad accumulation into main_grad)
+    moe_grouped_gemm_kernel: str = "torch"
     moe_token_dispatcher_type: str = "alltoall"  # 'alltoall' | 'allgather'
     moe_expert_capacity_factor: Optional[float] = None  # None -> dropless
     moe_token_drop_policy: str = "probs"  # 'probs' | 'position'

@@ -24,6 +24,9 @@ class GroupedMLP(nn.Module):
     def __init__(self, config):
         super().__init__()
         self.config = config
+        self.kernel = getattr(config, "moe_grouped_gemm_kernel", "torch")
+        if self.kernel not in ("torch", "hip"):
+            raise ValueError(f"moe_grouped_gemm_kernel must be 'torch' or 'hip', got {self.kernel!r}")
         ep = G.get_expert_model_parallel_world_size() if G.grid_initialized() else 1
         tp = G.get_tensor_model_parallel_world_size()
         self.num_local_experts = config.num_experts // max(ep, 1)
@@ -63,7 +66,20 @@ class GroupedMLP(nn.Module):
         — fc1 for all experts in one launch, fused activation, fc2 in one
         launch; the per-expert sizes sync below is the layer's single chosen
         host sync point (reference token_dispatcher.py:453-460).  CPU /
-        no-native: per-expert matmul loop."""
+        no-native: per-expert matmul loop.
+
+        moe_grouped_gemm_kernel="hip": the HIP grouped GEMMs take
+        tokens_per_expert as it is, on the device, so the layer reads nothing
+        on the host; rows past sum(tokens_per_expert) come out as zeros.
+        Shapes those kernels do not serve (ops.grouped_linear) take the
+        path below with its one host read."""
+        if (self.kernel == "hip" and tokens.is_cuda and tokens_per_expert.is_cuda and ops.has_native()
+                and ops._grouped_hip_serves(tokens, self.weight1)
+                and ops._grouped_hip_serves(tokens, self.weight2)):
+            h = ops.grouped_linear(tokens, self.weight1, tokens_per_expert, kernel="hip")
+            h = self._act(h)
+            out = ops.grouped_linear(h, self.weight2, tokens_per_expert, kernel="hip")
+            return self._reduce_output(out)
         if tokens_per_expert.is_cuda:
             splits = tokens_per_expert.cpu().tolist()  # single sync per layer
         else:
@@ -88,6 +104,9 @@ class GroupedMLP(nn.Module):
                 y = torch.matmul(h, self.weight2[e].t())
                 outs.append(y)
             out = torch.cat(outs, dim=0) if len(outs) > 1 else outs[0]
+        return self._reduce_output(out)
+
+    def _reduce_output(self, out):
         tp_group = G.get_tensor_model_parallel_group() if G.grid_initialized() else None
         if tp_group is not None and G.get_tensor_model_parallel_world_size() > 1:
             out = _ReduceExpertOutput.apply(out)

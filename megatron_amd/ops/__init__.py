@@ -551,9 +551,82 @@ class _GroupedLinearFnHipblaslt(torch.autograd.Function):
         return da, dw, None
 
 
-def grouped_linear(a: torch.Tensor, weight: torch.Tensor, sizes) -> torch.Tensor:
+class _GroupedLinearFnHip(torch.autograd.Function):
+    """The same product through the project's own grouped GEMM kernels
+    (csrc/grouped_gemm_hip.hip): `sizes` is an [E] int32/int64 device tensor
+    that is never read on the host, rows at or past sum(sizes) come out as
+    zeros, and wgrad accumulates in fp32 straight into weight.main_grad."""
+
+    @staticmethod
+    def forward(ctx, a, weight, sizes):
+        a = a.contiguous()
+        out = _C.grouped_gemm_hip(a, weight.contiguous(), sizes, True)
+        ctx.save_for_backward(a, weight, sizes)
+        return out
+
+    @staticmethod
+    def backward(ctx, dy):
+        a, weight, sizes = ctx.saved_tensors
+        dy = dy.contiguous()
+        da = _C.grouped_gemm_hip(dy, weight.contiguous(), sizes, False) if ctx.needs_input_grad[0] else None
+        main_grad = getattr(weight, "main_grad", None)
+        if main_grad is not None and main_grad.is_cuda and main_grad.dtype == torch.float32:
+            mg = main_grad.view(weight.shape)
+            if mg.data_ptr() % 16 == 0:
+                _C.grouped_gemm_hip_wgrad(dy, a, sizes, mg, True)
+            else:
+                # a slice of a flat grad buffer that starts off a 16-byte boundary: the
+                # kernel's 16-byte read-modify-write cannot address it; still an fp32 sum
+                dw32 = torch.zeros_like(mg)
+                _C.grouped_gemm_hip_wgrad(dy, a, sizes, dw32, True)
+                mg.add_(dw32)
+            weight.grad_added_to_main_grad = True
+            cb = getattr(weight, "_ddp_grad_ready_cb", None)
+            if cb is not None:
+                cb()
+            dw = None
+        else:
+            dw = torch.empty_like(weight, memory_format=torch.contiguous_format)
+            _C.grouped_gemm_hip_wgrad(dy, a, sizes, dw, False)
+        return da, dw, None
+
+
+def _grouped_hip_serves(a: torch.Tensor, weight: torch.Tensor) -> bool:
+    return (
+        a.dtype == torch.bfloat16 and weight.dtype == torch.bfloat16
+        and weight.shape[0] <= 256 and weight.shape[1] % 64 == 0 and weight.shape[2] % 64 == 0
+        and a.shape[0] < 2**31 - 512
+    )
+
+
+def grouped_linear(a: torch.Tensor, weight: torch.Tensor, sizes, kernel: str = "torch") -> torch.Tensor:
     """a [M, k] bf16 rows grouped by expert; weight [E, n, k]; sizes: host
-    ints per expert summing to M.  Returns [M, n]."""
+    ints per expert summing to M.  Returns [M, n].
+
+    kernel="hip" runs the project's own grouped GEMM kernels: `sizes` may then
+    be an [E] integer device tensor, used as it is with no host read (a list is
+    uploaded), and may sum to less than M: the rows past the sum come out as
+    zeros.  Other dtypes than bf16, n or k that is no multiple of 64, more than
+    256 experts, 2^31 - 512 rows or more and CPU tensors take the path of
+    kernel="torch", which reads the sizes on the host; the zero rows past the
+    sum are kept there, the kernels' clamping of negative or too large sizes
+    is not."""
+    if kernel not in ("torch", "hip"):
+        raise ValueError(f"grouped_linear kernel must be 'torch' or 'hip', got {kernel!r}")
+    if kernel == "hip" and _use_native(a) and _grouped_hip_serves(a, weight):
+        if not torch.is_tensor(sizes):
+            sizes = torch.tensor([int(s) for s in sizes], dtype=torch.int64)
+        if sizes.dtype not in (torch.int32, torch.int64):
+            sizes = sizes.long()
+        sizes = sizes.to(a.device).contiguous()
+        return _GroupedLinearFnHip.apply(a, weight, sizes)
+    if torch.is_tensor(sizes):
+        sizes = sizes.tolist()
+    if kernel == "hip":
+        live = sum(int(s) for s in sizes)
+        if live < a.shape[0]:
+            out = grouped_linear(a[:live], weight, sizes)
+            return torch.cat([out, out.new_zeros(a.shape[0] - live, out.shape[1])], dim=0)
     if _use_native(a):
         fn = _GroupedLinearFn if _USE_TORCH_GROUPED else _GroupedLinearFnHipblaslt
         return fn.apply(a, weight, tuple(int(s) for s in sizes))

@@ -40,6 +40,9 @@ void ce_bwd(torch::Tensor logits, torch::Tensor target, torch::Tensor row_max,
 std::string grouped_gemm_probe();
 torch::Tensor grouped_gemm(torch::Tensor a, torch::Tensor b, std::vector<int64_t> sizes, bool trans_b);
 void grouped_gemm_wgrad(torch::Tensor dy, torch::Tensor x, std::vector<int64_t> sizes, torch::Tensor dw);
+torch::Tensor grouped_gemm_hip(torch::Tensor a, torch::Tensor b, torch::Tensor sizes, bool trans_b);
+void grouped_gemm_hip_wgrad(torch::Tensor dy, torch::Tensor x, torch::Tensor sizes, torch::Tensor dw,
+                            bool accumulate);
 std::vector<torch::Tensor> causal_conv1d_fwd(torch::Tensor x, torch::Tensor w, torch::Tensor bias);
 std::vector<torch::Tensor> causal_conv1d_bwd(torch::Tensor dy, torch::Tensor x,
                                              torch::Tensor pre, torch::Tensor w);
@@ -80,6 +83,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("grouped_gemm", &grouped_gemm);
   m.def("grouped_gemm_probe", &grouped_gemm_probe);
   m.def("grouped_gemm_wgrad", &grouped_gemm_wgrad);
+  m.def("grouped_gemm_hip", &grouped_gemm_hip);
+  m.def("grouped_gemm_hip_wgrad", &grouped_gemm_hip_wgrad);
   m.def("causal_conv1d_fwd", &causal_conv1d_fwd);
   m.def("causal_conv1d_bwd", &causal_conv1d_bwd);
   m.def("ssd_scan_fwd", &ssd_scan_fwd);

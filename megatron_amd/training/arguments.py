@@ -91,6 +91,9 @@ def build_arg_parser() -> argparse.ArgumentParser:
     g.add_argument("--moe-layer-freq", type=_moe_freq, default=1,
                    help="int N (every Nth layer is MoE) or a 0/1 list like [0,0,1,1]")
     g.add_argument("--moe-router-pre-softmax", action="store_true", default=False)
+    g.add_argument("--moe-grouped-gemm-kernel", choices=["torch", "hip"], default="torch",
+                   help="expert GEMMs: torch._grouped_mm, or the HIP grouped GEMM kernels "
+                        "(expert sizes stay on the device, fp32 wgrad into main_grad)")
     g.add_argument("--moe-router-num-groups", type=int, default=None)
     g.add_argument("--moe-router-group-topk", type=int, default=None)
     g.add_argument("--moe-input-jitter-eps", type=float, default=None)
@@ -347,6 +350,7 @@ def configs_from_args(args):
         moe_layer_freq=args.moe_layer_freq,
         moe_router_force_load_balancing=args.moe_router_force_load_balancing,
         moe_router_pre_softmax=args.moe_router_pre_softmax,
+        moe_grouped_gemm_kernel=args.moe_grouped_gemm_kernel,
         moe_router_num_groups=args.moe_router_num_groups,
         moe_router_group_topk=args.moe_router_group_topk,
         moe_input_jitter_eps=args.moe_input_jitter_eps,
