@@ -46,7 +46,7 @@ class ParallelConfig:
     num_layers_in_first_pipeline_stage: Optional[int] = None
     num_layers_in_last_pipeline_stage: Optional[int] = None
     sequence_parallel: bool = False
-    fp8: object = None  # None | 'hybrid' | 'e4m3' (K15)
+    fp8: object = None  # None | 'hybrid' | 'e4m3' | 'mxfp8' (K15)
     fp8_amax_history_len: int = 16
     fp8_margin: int = 0
     # expert tensor parallel size (defaults to tensor_parallel_size)

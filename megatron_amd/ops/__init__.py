@@ -639,6 +639,47 @@ def grouped_linear(a: torch.Tensor, weight: torch.Tensor, sizes, kernel: str = "
 
 
 # ---------------------------------------------------------------------------
+# MXFP8 quantise and block-scaled GEMM  (K15)
+# ---------------------------------------------------------------------------
+
+
+def _mx_aligned(*tensors) -> bool:
+    return all(t.is_contiguous() and t.data_ptr() % 16 == 0 for t in tensors)
+
+
+def mx_quantize(t: torch.Tensor, dual: bool = False):
+    """t [R, K] -> (q e4m3 [R, K], s uint8 [R, K/32]): e8m0 scale bytes per
+    block of 32 along K (format in ops/mxfp8.py).  dual=True also returns
+    (qT [K, R], sT [K, R/32]), the quantisation of t^T, from the same read.
+    HIP kernel for bf16 on the GPU; anything else takes the torch reference."""
+    from megatron_amd.ops import mxfp8
+
+    t = t.contiguous()
+    if (
+        _use_native(t) and t.dtype == torch.bfloat16 and t.dim() == 2 and t.shape[0] > 0
+        and t.shape[1] % 32 == 0 and (not dual or t.shape[0] % 32 == 0) and _mx_aligned(t)
+    ):
+        return tuple(_C.mx_quantize(t, dual))
+    return mxfp8.quantize_mxfp8_dual(t) if dual else mxfp8.quantize_mxfp8(t)
+
+
+def mx_gemm_nt(aq: torch.Tensor, a_s: torch.Tensor, bq: torch.Tensor, b_s: torch.Tensor) -> torch.Tensor:
+    """bf16 [M, N] = dequant(aq [M, K], a_s) @ dequant(bq [N, K], b_s)^T with
+    fp32 accumulation.  HIP kernel for K % 128 == 0, N % 16 == 0 and 16-byte
+    aligned contiguous operands on the GPU; anything else takes the reference
+    (dequantise, matmul in fp32, round to bf16)."""
+    from megatron_amd.ops import mxfp8
+
+    if (
+        _use_native(aq) and aq.dim() == 2 and bq.dim() == 2 and aq.shape[0] >= 1
+        and aq.shape[1] % 128 == 0 and bq.shape[0] % 16 == 0 and bq.shape[0] > 0
+        and aq.shape[1] < 2**24 and _mx_aligned(aq, a_s, bq, b_s)
+    ):
+        return _C.mx_gemm_nt(aq, a_s, bq, b_s)
+    return mxfp8.gemm_nt_reference(aq, a_s, bq, b_s)
+
+
+# ---------------------------------------------------------------------------
 # multi-tensor optimizer kernels  (K10)
 # ---------------------------------------------------------------------------
 

@@ -43,6 +43,8 @@ void grouped_gemm_wgrad(torch::Tensor dy, torch::Tensor x, std::vector<int64_t> 
 torch::Tensor grouped_gemm_hip(torch::Tensor a, torch::Tensor b, torch::Tensor sizes, bool trans_b);
 void grouped_gemm_hip_wgrad(torch::Tensor dy, torch::Tensor x, torch::Tensor sizes, torch::Tensor dw,
                             bool accumulate);
+std::vector<torch::Tensor> mx_quantize(torch::Tensor t, bool dual);
+torch::Tensor mx_gemm_nt(torch::Tensor aq, torch::Tensor a_s, torch::Tensor bq, torch::Tensor b_s);
 std::vector<torch::Tensor> causal_conv1d_fwd(torch::Tensor x, torch::Tensor w, torch::Tensor bias);
 std::vector<torch::Tensor> causal_conv1d_bwd(torch::Tensor dy, torch::Tensor x,
                                              torch::Tensor pre, torch::Tensor w);
@@ -85,6 +87,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("grouped_gemm_wgrad", &grouped_gemm_wgrad);
   m.def("grouped_gemm_hip", &grouped_gemm_hip);
   m.def("grouped_gemm_hip_wgrad", &grouped_gemm_hip_wgrad);
+  m.def("mx_quantize", &mx_quantize);
+  m.def("mx_gemm_nt", &mx_gemm_nt);
   m.def("causal_conv1d_fwd", &causal_conv1d_fwd);
   m.def("causal_conv1d_bwd", &causal_conv1d_bwd);
   m.def("ssd_scan_fwd", &ssd_scan_fwd);

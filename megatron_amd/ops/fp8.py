@@ -118,7 +118,13 @@ def fp8_eligible(x: torch.Tensor, w: torch.Tensor) -> bool:
 
 def make_recipes(fmt: str = "hybrid", history_len: int = 16, margin: int = 0):
     """(input, weight, grad) recipes. 'hybrid' = e4m3 fwd + e5m2 grads
-    (reference TE Format.HYBRID); 'e4m3' clamps grads to e4m3 range too."""
+    (reference TE Format.HYBRID); 'e4m3' clamps grads to e4m3 range too.
+    'mxfp8' returns one MXFP8Recipe marker instead: block scales need no amax
+    history (ops/mxfp8.py)."""
+    if fmt == "mxfp8":
+        from megatron_amd.ops.mxfp8 import MXFP8Recipe
+
+        return MXFP8Recipe()
     gmax = E5M2_MAX if fmt == "hybrid" else E4M3_MAX
     return (DelayedScaling(history_len, margin, E4M3_MAX),
             DelayedScaling(history_len, margin, E4M3_MAX),

@@ -78,6 +78,7 @@ class _ParallelLinearFn(torch.autograd.Function):
 
             ctx.save_for_backward(inp, weight)
             ctx.fp8 = False
+            ctx.mxfp8 = False
             group = G.get_tensor_model_parallel_group()
             world = dist.get_world_size(group) if dist.is_initialized() else 1
             x2 = inp.reshape(-1, inp.shape[-1])
@@ -101,10 +102,21 @@ class _ParallelLinearFn(torch.autograd.Function):
             total_input = inp
         ctx.save_for_backward(inp, weight)
         ctx.fp8 = False
+        ctx.mxfp8 = False
         if fp8_recipes is not None:
             from megatron_amd.ops import fp8 as F8
+            from megatron_amd.ops import mxfp8 as MX
 
-            if F8.fp8_eligible(total_input, weight):
+            if isinstance(fp8_recipes, MX.MXFP8Recipe):
+                if MX.mxfp8_eligible(total_input, weight):
+                    x2d = total_input.reshape(-1, total_input.shape[-1])
+                    output, ctx.wqT, ctx.wsT = MX.linear_fwd(x2d, weight)
+                    output = output.reshape(*total_input.shape[:-1], weight.shape[0])
+                    ctx.mxfp8 = True
+                    if bias is not None:
+                        output = output + bias
+                    return output
+            elif F8.fp8_eligible(total_input, weight):
                 rx, rw, rg = fp8_recipes
                 x2d = total_input.reshape(-1, total_input.shape[-1])
                 xq, inv_x = F8.quantize_fp8(x2d, rx.scale_for(x2d))
@@ -150,7 +162,13 @@ class _ParallelLinearFn(torch.autograd.Function):
             total_input = inp
             gather_handle = None
 
-        if ctx.fp8:
+        if ctx.mxfp8:
+            from megatron_amd.ops import mxfp8 as MX
+
+            go2d = grad_output.reshape(-1, grad_output.shape[-1])
+            grad_input = MX.linear_dgrad(go2d, ctx.wqT, ctx.wsT)
+            grad_input = grad_input.reshape(*grad_output.shape[:-1], weight.shape[1])
+        elif ctx.fp8:
             from megatron_amd.ops import fp8 as F8
 
             go2d = grad_output.reshape(-1, grad_output.shape[-1])

@@ -162,7 +162,7 @@ def build_arg_parser() -> argparse.ArgumentParser:
     g.add_argument("--recompute-granularity", choices=["full", "selective"], default=None)
     g.add_argument("--recompute-num-layers", type=int, default=None)
     g.add_argument("--bf16", action="store_true")
-    g.add_argument("--fp8-format", choices=["hybrid", "e4m3"], default=None)
+    g.add_argument("--fp8-format", choices=["hybrid", "e4m3", "mxfp8"], default=None)
     g.add_argument("--fp8-amax-history-len", type=int, default=16)
     g.add_argument("--fp8-margin", type=int, default=0)
     g.add_argument("--fp16", action="store_true")

@@ -24,6 +24,8 @@ SRC = [
     "megatron_amd/ops/csrc/cross_entropy.hip",
     "megatron_amd/ops/csrc/grouped_gemm.cpp",
     "megatron_amd/ops/csrc/grouped_gemm_hip.hip",
+    "megatron_amd/ops/csrc/mx_quant.hip",
+    "megatron_amd/ops/csrc/mx_gemm.hip",
     "megatron_amd/ops/csrc/causal_conv1d.hip",
     "megatron_amd/ops/csrc/ssd_scan.hip",
     "megatron_amd/ops/csrc/attention_fwd.hip",
